@@ -10,19 +10,18 @@ fp16 MFMA rate a bare MFMA loop sustains on random data on THIS box right after 
 (yolo_mfma_probe) -- and, at N = 1, a `cpu_baseline` (the torch-CPU restatement of the same training step on
 the host cores; tf.keras is not installable here).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes what the last timed step computed to DIR/<name>.npy (dump_outputs), so that two builds run with
+the same arguments -- same seeds, same weights, same batch -- can be compared output for output.
 """
 import argparse
 import json
 import os
 import sys
 import time
-
-# More hardware queues than the runtime's default of 4: a data-parallel rank runs four or five streams, and with 4 queues the two
-# compute streams of the step shared one (34.2 instead of 30.1 ms per step; tf2_yolo_amd/__init__.py). Read at HIP initialisation.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 import numpy as np
 import torch
@@ -377,9 +376,35 @@ def configs_block():
     return res
 
 
+DUMP_SAMPLE = 1 << 22   # elements kept of a longer buffer by --dump-outputs: 16 MB of float32
+
+
+def dump_outputs(path, model, bufs):
+    """--dump-outputs: what the last timed step computed, as a caller of Model.train_step_device receives it -- the loss
+    buffers the call returned (float64, one row per output level, element 0 = that level's loss) and the model state it left
+    behind (float32: the trainable parameters after the optimizer step, the BatchNorm moving statistics). A buffer longer than
+    DUMP_SAMPLE is written as a fixed sample: indices drawn from default_rng(0) and sorted, the same elements in every run
+    (YOLOv3-416 at C = 80 has 62 M parameters, 250 MB). The weights and statistics repeat bit for bit from run to run; the
+    losses are float64 sums over workgroups in arrival order (csrc/loss.hip) and repeat to about one ulp. Returns {name: shape}."""
+    os.makedirs(path, exist_ok=True)
+
+    def sample(t):
+        if t.numel() <= DUMP_SAMPLE:
+            return t
+        idx = np.sort(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+        return t[torch.from_numpy(idx).to(t.device)]
+
+    arrays = {"loss_buffers": torch.stack([b.detach() for b in bufs]).double(),
+              "params": sample(model.net.params.data).float(),
+              "bn_moving_stats": sample(model.net.state.data).float()}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+    return {name: list(t.shape) for name, t in arrays.items()}
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` without a torchrun environment: start N fresh child processes of this file, one rank per
-    GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* and GPU_MAX_HW_QUEUES in their environment), relay rank 0's JSON line and
+    GPU (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment), relay rank 0's JSON line and
     return the exit code (non-zero if any rank failed). The parent never touches the GPU (torch.cuda.device_count() does not
     initialise HIP on this image) and never re-execs itself. With fewer visible devices than ranks the job degrades to the
     visible count and says so; returns None when that leaves one rank (the caller then runs the N = 1 job itself).
@@ -404,11 +429,12 @@ def launch_ranks(args):
     for flag in ("no_cpu_baseline", "no_kernel_timer", "no_extra_blocks", "plain"):
         if getattr(args, flag):
             argv.append("--" + flag.replace("_", "-"))
+    if args.dump_outputs is not None:
+        argv += ["--dump-outputs", args.dump_outputs]
     procs = []
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        env.setdefault("GPU_MAX_HW_QUEUES", "8")
         procs.append(subprocess.Popen(argv, env=env, stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, text=True))
     # rank 0's stdout is the job's stdout; a rank that dies takes the others down (they would wait in a collective for ever)
     import threading
@@ -450,7 +476,11 @@ def main():
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-extra-blocks", action="store_true", help="skip strict_fp32 / configs (profiling runs)")
     ap.add_argument("--plain", action="store_true", help="timed region only; prints {ms_per_step, images_per_s, loss}")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process (which has made NO GPU call) becomes the launcher of N ranks
@@ -540,6 +570,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     log(f"timed region done: {dt / args.steps * 1e3:.2f} ms/step")
+    if args.dump_outputs is not None and rank == 0:   # (before the steps below move the weights on)
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {dump_outputs(args.dump_outputs, model, bufs)}")
     loss_val = float(sum(b[0].item() for b in bufs))
     if args.plain:
         if rank == 0:

@@ -9,7 +9,6 @@ L+1 need conv_B(L+1) too, so apply_A(L+1) cannot start before it). This probe ru
 (finalize kernels left out of both: identical in both; BN coefficients fixed.) usage: half_batch_probe.py out.json"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from tf2_yolo_amd import ops
 ops.ensure_conv_workspace()

@@ -6,7 +6,6 @@ ratio concurrent / (sum of alone): 1.0 = nothing gained by overlapping, 0.5 = th
 with the filter-gradient stream at low priority. usage: pair_matrix.py out.json"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import torch
 from tf2_yolo_amd import ops
 out_path = sys.argv[1] if len(sys.argv) > 1 else None

@@ -3,7 +3,6 @@ training steps alternating between them, wall time per step of each block.
 usage: step_ab.py [--config c3|c4] [--k K] [--rounds R] NAME:VAR=VAL[,VAR=VAL...] NAME:... (an empty setting list = defaults)"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 
 ap = argparse.ArgumentParser()

@@ -6,7 +6,6 @@ BatchNorm statistics unsplit. (Only options whose results stay correct: a knock-
 different power state, not the step.)"""
 import argparse, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 
 ap = argparse.ArgumentParser()

@@ -3,7 +3,6 @@ the same batch (one after the other, same process); after every step their param
 the first tensors that differ are named. usage: step_repro.py c1|c2|c3|c4 [steps] [batch]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np, torch
 from tf2_yolo_amd import graphs, labels, optimizers, ops
 ops.create_side_streams()

@@ -82,7 +82,6 @@ def test_bench_starts_its_own_ranks_without_a_torchrun_environment():
     j = _json_line(r.stdout)
     assert j["n_gpus"] == 2 and j["config"]["global_batch"] == 8 and j["scaling"] == "weak"
     assert j["config"]["replicas_in_sync"] is True
-    assert "GPU_MAX_HW_QUEUES=8 does not apply" not in r.stderr
     bad = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--batch", "-1"] + ARGS[:4], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0

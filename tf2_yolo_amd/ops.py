@@ -201,8 +201,8 @@ def ensure_wgrad_workspace():
 
 
 # ---- side streams of the process: created ONCE, EARLY, in a fixed order ----
-# The ROCm runtime maps HIP streams onto a few hardware queues (GPU_MAX_HW_QUEUES; tf2_yolo_amd/__init__.py raises the default
-# of 4 to 8) in creation order, wrapping around, and two streams on one queue execute one after the other. Measured (round 4,
+# The ROCm runtime maps HIP streams onto a few hardware queues (GPU_MAX_HW_QUEUES) in creation order, wrapping around, and two
+# streams on one queue execute one after the other. Measured (round 4,
 # profiles/r04_b_dp_*): with RCCL initialised first, the filter-gradient stream -- created lazily in the first forward pass --
 # landed on the compute stream's queue: 34.2 instead of 30.1 ms per step; as the fourth model of one process, YOLOv4-608's own
 # filter-gradient stream did the same: 58.8 instead of 39.7 ms. So the process has ONE stream per role, shared by every model,
