@@ -733,7 +733,16 @@ def _conv_small_takes(rows, cout, k, cin):
     return g11 <= (grid or 256) or g22 <= (grid or 256)
 
 
-@pytest.mark.parametrize("case,with_res,expect_onepass", [
+def _conv_small_head_tile(rows, cout):
+    """the launch policy of csrc/conv_small.hip for the detection head (small_head_tile): 11 (32 x 32), 22 (64 x 64) or 0"""
+    if int(os.environ.get("YOLO_CONV_SMALL", "1")) == 0:
+        return 0
+    g11 = ((rows + 31) // 32) * ((cout + 31) // 32)
+    g22 = ((rows + 63) // 64) * ((cout + 63) // 64)
+    return 11 if g11 <= 256 else 22 if g22 <= 256 else 0
+
+
+INFER_UNIT_CASES = [
     ((1, 13, 13, 512, 1024, 3, 1, "same", False), True, True),    # window kernel, split-K: the reduce kernel writes the planes
     ((1, 26, 26, 512, 256, 1, 1, "same", False), False, True),   # per-tap kernel, split-K
     ((1, 52, 52, 128, 256, 3, 1, "same", True), True, True),     # conv bias in front of the folded BatchNorm
@@ -748,12 +757,26 @@ def _conv_small_takes(rows, cout, k, cin):
     ((1, 20, 20, 16, 32, 1, 1, "same", False), True, None),      # ONE step: seven waves multiply by the zero block
     ((1, 26, 26, 128, 64, 1, 2, "same", False), False, None),    # 1x1 stride 2
     ((1, 104, 104, 64, 128, 3, 1, "same", False), True, None),   # 338 workgroups of 64 x 64: two rounds
-])
+]
+
+
+@pytest.mark.parametrize("case,with_res,expect_onepass", INFER_UNIT_CASES)
 def test_inference_unit_writes_its_planes(case, with_res, expect_onepass):
     """yolo_conv2d_fwd_infer_unit: y bit-identical to the fused-epilogue convolution, its planes (scaled by the a-priori
     bound K max|x| + D + max|residual|, yolo_conv_pred_bound) hold y to the format's 22 bits, the recorded bound of the
     result is max|y| (one pass: one word per workgroup) or an upper bound of it (two passes inside the call)"""
+    _inference_unit_writes_its_planes(case, with_res, expect_onepass, "leaky")
+
+
+@pytest.mark.parametrize("case,with_res,expect_onepass", INFER_UNIT_CASES)
+def test_inference_unit_writes_its_planes_mish(case, with_res, expect_onepass):
+    """test_inference_unit_writes_its_planes with the affine + Mish epilogue of the YOLOv4 units"""
+    _inference_unit_writes_its_planes(case, with_res, expect_onepass, "mish")
+
+
+def _inference_unit_writes_its_planes(case, with_res, expect_onepass, epi):
     from tf2_yolo_amd import ops
+    epi_code = ops.EPI_AFFINE_LEAKY if epi == "leaky" else ops.EPI_AFFINE_MISH
     ops.ensure_conv_workspace()   # (split-K needs its slabs: the engine registers them when a network is built)
     n, h, w, cin, cout, k, s, pad, bias = case
     x, wk, b = _mk(case, seed=21)
@@ -768,7 +791,7 @@ def test_inference_unit_writes_its_planes(case, with_res, expect_onepass):
     xp = ops.split_planes(xd, n * h * w, cin)
     wp = ops.split_planes(wd, cout, k * k * cin)
     amax0 = torch.zeros(cout, device="cuda", dtype=torch.int32)
-    y_ref = ops.conv2d_fwd_planes_epi(d, xp, wp, bd, ops.EPI_AFFINE_LEAKY, scale, shift, residual=res, absmax=amax0)
+    y_ref = ops.conv2d_fwd_planes_epi(d, xp, wp, bd, epi_code, scale, shift, residual=res, absmax=amax0)
     in_bound = xd.abs().max().reshape(1)
     res_bound = res.abs().max().reshape(1) if with_res else None
     pred = torch.zeros(2, device="cuda")
@@ -786,7 +809,7 @@ def test_inference_unit_writes_its_planes(case, with_res, expect_onepass):
     in_words = torch.zeros(777, device="cuda")
     in_words[torch.randint(0, 777, (40,), generator=g)] = in_bound * 0.5
     in_words[500] = in_bound
-    nw = ops.conv2d_fwd_infer_unit(d, xp, wp, bd, ops.EPI_AFFINE_LEAKY, scale, shift, res, y, amax, pred,
+    nw = ops.conv2d_fwd_infer_unit(d, xp, wp, bd, epi_code, scale, shift, res, y, amax, pred,
                                    in_words.view(torch.int32), res_bound, pl, out_words, out_bound)
     torch.cuda.synchronize()
     assert expect_onepass is None or (nw > 0) == expect_onepass
@@ -845,10 +868,23 @@ def _small_fuzz_cases():
 @pytest.mark.parametrize("case", _small_fuzz_cases())
 def test_conv_small_kernel_random_shapes(case):
     """yolo_conv2d_fwd_infer_unit on 24 random small shapes (1x1 and 3x3, strides 1 / 2, 'same' / 'valid', 1-3 images, odd
-    sizes, Cin = 16 .. 192, Cout = 32 .. 256, with and without a residual): whichever kernel the policy picks
-    (csrc/conv_small.hip for the 1x1 units and, under YOLO_CONV_SMALL=3 -- scripts/gpu/r6aw.sh runs the file that way too --
-    for every 3x3 unit) against the float64 oracle and the fused-epilogue convolution of the training kernels."""
+    sizes, Cin = 16 .. 192, Cout = 32 .. 256, with and without a residual), affine + LeakyReLU and affine + Mish epilogues:
+    whichever kernel the policy picks (csrc/conv_small.hip for the 1x1 units and, under YOLO_CONV_SMALL=3 -- which
+    tests/test_gpu_infer_bs1.py::test_c5_library_switches_in_child_processes runs this file under, also with the 32 x 64 and
+    64 x 64 tiles forced -- for every 3x3 unit) against the float64 oracle and the fused-epilogue convolution of the
+    training kernels."""
+    _conv_small_kernel_random_shapes(case, "leaky")
+
+
+@pytest.mark.parametrize("case", _small_fuzz_cases())
+def test_conv_small_kernel_random_shapes_mish(case):
+    """test_conv_small_kernel_random_shapes with the affine + Mish epilogue"""
+    _conv_small_kernel_random_shapes(case, "mish")
+
+
+def _conv_small_kernel_random_shapes(case, epi):
     from tf2_yolo_amd import ops
+    epi_code = ops.EPI_AFFINE_LEAKY if epi == "leaky" else ops.EPI_AFFINE_MISH
     ops.ensure_conv_workspace()
     n, h, w, cin, cout, k, s, pad, bias = case
     x, wk, b = _mk(case, seed=51)
@@ -864,20 +900,20 @@ def test_conv_small_kernel_random_shapes(case):
     xp = ops.split_planes(xd, n * h * w, cin)
     wp = ops.split_planes(wd, cout, k * k * cin)
     amax0 = torch.zeros(cout, device="cuda", dtype=torch.int32)
-    y_ref = ops.conv2d_fwd_planes_epi(d, xp, wp, bd, ops.EPI_AFFINE_LEAKY, scale, shift, residual=res, absmax=amax0)
+    y_ref = ops.conv2d_fwd_planes_epi(d, xp, wp, bd, epi_code, scale, shift, residual=res, absmax=amax0)
     pred = torch.zeros(2, device="cuda")
     ops.conv_pred_bound(wd, cout, k * k * cin, scale, shift, bd, pred)
     y = torch.full_like(y_ref, float("nan"))
     pl = torch.zeros(ops.planes_bytes(rows, cout), device="cuda", dtype=torch.uint8)
     out_words = torch.full((ops.INFER_BOUND_WORDS,), -1, device="cuda", dtype=torch.int32)
-    nw = ops.conv2d_fwd_infer_unit(d, xp, wp, bd, ops.EPI_AFFINE_LEAKY, scale, shift, res, y,
+    nw = ops.conv2d_fwd_infer_unit(d, xp, wp, bd, epi_code, scale, shift, res, y,
                                    torch.zeros(cout, device="cuda", dtype=torch.int32), pred, xd.abs().max().reshape(1),
                                    res.abs().max().reshape(1) if with_res else None, pl, out_words, torch.zeros(1, device="cuda"))
     torch.cuda.synchronize()
     assert _relerr(y.double(), y_ref.double()) < 2e-6
     ref = L.conv2d(x, wk, b, stride=s, padding=pad)
     z = ref.permute(0, 1, 2, 3) * scale.double().cpu() + shift.double().cpu()
-    z = torch.where(z > 0, z, 0.1 * z) + (res.double().cpu() if with_res else 0.0)
+    z = (L.leaky(z) if epi == "leaky" else L.mish(z)) + (res.double().cpu() if with_res else 0.0)
     assert _relerr(y.double().cpu(), z) < 1e-5
     vals, bound, sc, tail = _planes_values(pl.cpu(), rows, cout)
     assert (tail == 0).all() and bound >= float(y.abs().max())
@@ -887,13 +923,21 @@ def test_conv_small_kernel_random_shapes(case):
         assert float(out_words[:nw].view(torch.float32).max()) == float(y.abs().max())
 
 
+# Cout 75 / 75 / 32 on the 64 x 64 tile, whose filter rows run past the zero block of the weight planes (the head unit
+# takes Cout >= 32: a C = 3 head of three anchors, 24 channels, runs convolution + activation in the engine instead)
+HEAD_TILE22_CASES = [(2, 52, 256, 3, 20, 3), (1, 76, 256, 3, 20, 4), (2, 76, 256, 4, 3, 4)]
+
+
 @pytest.mark.parametrize("n,hw,cin,A,C,version", [(1, 13, 1024, 3, 80, 3), (1, 26, 512, 3, 80, 3), (1, 52, 256, 3, 80, 4),
-                                                  (2, 19, 128, 3, 20, 3), (1, 13, 1024, 5, 20, 2), (8, 52, 256, 3, 80, 3)])
+                                                  (2, 19, 128, 3, 20, 3), (1, 13, 1024, 5, 20, 2), (8, 52, 256, 3, 80, 3)]
+                         + HEAD_TILE22_CASES)
 def test_head_unit_in_one_call(n, hw, cin, A, C, version):
-    """yolo_conv2d_fwd_head_unit (round 6): the head's 1x1 convolution (bias, Cout = A (5 + C): 255, 75, 125 -- not a
-    multiple of 16) and its activation; at few output pixels ONE launch (csrc/conv_small.hip, v3 / v4), otherwise
+    """yolo_conv2d_fwd_head_unit (round 6): the head's 1x1 convolution (bias, Cout = A (5 + C): 255, 75, 125, 32 -- mostly not
+    a multiple of 16) and its activation; at few output pixels ONE launch (csrc/conv_small.hip, v3 / v4), otherwise
     (v2's softmax, many pixels) convolution + yolo_head_act_fwd behind the same entry. Against those two calls: t to fp32
-    summation order, y to the activation's conditioning (yolov3/models/__init__.py:34-64)."""
+    summation order, y to the activation's conditioning (yolov3/models/__init__.py:34-64). The 64 x 64 tile cases run
+    again with the weight planes as a view at the front of a larger buffer whose tail is NaN: t and y must not change
+    (the filter rows past Cout read the planes' zero block, never the bytes behind the planes)."""
     from tf2_yolo_amd import ops
     ops.ensure_conv_workspace()
     g = torch.Generator().manual_seed(31)
@@ -917,6 +961,18 @@ def test_head_unit_in_one_call(n, hw, cin, A, C, version):
     # y: exactly the head activation of the t this call wrote
     assert torch.equal(y, ops.head_act_fwd(t, A, C, version, anchors))
     assert torch.allclose(y, y_ref, rtol=2e-5, atol=1e-6)
+    if (n, hw, cin, A, C, version) in HEAD_TILE22_CASES:
+        assert _conv_small_head_tile(n * hw * hw, cout) == (0 if os.environ.get("YOLO_CONV_SMALL") == "0" else 22)
+        pb = ops.planes_bytes(cout, cin)
+        wbuf = torch.full((2 * pb,), 0xFF, device="cuda", dtype=torch.uint8)   # 0xFFFF: a NaN in every fp16 plane
+        wbuf[:pb].copy_(wp)
+        t2 = torch.full_like(t_ref, float("nan"))
+        y2 = torch.full_like(t_ref, float("nan"))
+        ops.conv2d_fwd_head_unit(d, xp, wbuf[:pb], b, A, C, version, anchors, t2, y2)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(t2).all()) and bool(torch.isfinite(y2).all())
+        assert torch.equal(t2, t) and torch.equal(y2, y)
+        assert bool((wbuf[pb:] == 0xFF).all())
 
 
 @pytest.mark.parametrize("shape,act,with_y", [((2, 37, 45), "leaky", True), ((1, 64, 64), "mish", False),

@@ -116,7 +116,10 @@ __global__ __launch_bounds__(64 * SM_WAVES) void conv_small_kernel(const GatherC
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int crow = tile_n * BNT + 32 * j + r;
-    boff[j] = (unsigned)((crow >> 4) * (a.ldw >> 4)) * PL_RECORD + (unsigned)(crow & 15) * 16 + lane_unit;
+    // rows past the zero block (a head's 64-filter tile at Cout 32 / 75) would read beyond the planes body: the zero block
+    // holds all ldw / 16 records, and their columns are masked on store
+    const int cb = min(crow >> 4, a.zero_blk_wgt);
+    boff[j] = (unsigned)(cb * (a.ldw >> 4)) * PL_RECORD + (unsigned)(crow & 15) * 16 + lane_unit;
   }
   // steps past the end multiply by the all-zero block of the weights (no branch in the loop)
   const unsigned bzero = (unsigned)(a.zero_blk_wgt * (a.ldw >> 4)) * PL_RECORD + (unsigned)(r & 15) * 16 + lane_unit;
