@@ -17,9 +17,11 @@ ANCH9 = [[0.89663461, 0.78365384], [0.375, 0.47596153], [0.27884615, 0.21634615]
 
 
 def make_case(N, g, A, C, anchors, seed, v1=False, obj_frac=0.15):
+    """g: the grid, one number for a square one or (gh, gw)"""
+    gh, gw = (g, g) if np.isscalar(g) else g
     rng = np.random.default_rng(seed)
-    yt = np.zeros((N, g, g, 5 + C), dtype=np.float32)
-    mask = rng.random((N, g, g)) < obj_frac
+    yt = np.zeros((N, gh, gw, 5 + C), dtype=np.float32)
+    mask = rng.random((N, gh, gw)) < obj_frac
     n = int(mask.sum())
     yt[mask, 0:2] = rng.random((n, 2))
     yt[mask, 2:4] = rng.random((n, 2)) * 0.5 + 0.03
@@ -29,20 +31,20 @@ def make_case(N, g, A, C, anchors, seed, v1=False, obj_frac=0.15):
     tmp[np.arange(n), cls] = 1
     yt[mask, 5:] = tmp
     if v1:
-        yp = rng.random((N, g, g, 5 * A + C)).astype(np.float32) * 0.98 + 0.01
-        e = np.exp(rng.standard_normal((N, g, g, C)))
+        yp = rng.random((N, gh, gw, 5 * A + C)).astype(np.float32) * 0.98 + 0.01
+        e = np.exp(rng.standard_normal((N, gh, gw, C)))
         yp[..., 5 * A:] = e / e.sum(-1, keepdims=True)
     else:
-        yp = np.zeros((N, g, g, A, 5 + C), dtype=np.float32)
-        yp[..., 0:2] = rng.random((N, g, g, A, 2))
+        yp = np.zeros((N, gh, gw, A, 5 + C), dtype=np.float32)
+        yp[..., 0:2] = rng.random((N, gh, gw, A, 2))
         anc = np.array(anchors, dtype=np.float32).reshape(1, 1, 1, A, 2)
-        yp[..., 2:4] = np.exp(rng.standard_normal((N, g, g, A, 2)) * 0.5) * anc
-        yp[..., 4] = rng.random((N, g, g, A))
-        yp[..., 5:] = rng.random((N, g, g, A, C)) * 0.98 + 0.01
+        yp[..., 2:4] = np.exp(rng.standard_normal((N, gh, gw, A, 2)) * 0.5) * anc
+        yp[..., 4] = rng.random((N, gh, gw, A))
+        yp[..., 5:] = rng.random((N, gh, gw, A, C)) * 0.98 + 0.01
         # make some predictions overlap their truth strongly so the ignore / truth thresholds fire
-        sel = mask & (rng.random((N, g, g)) < 0.5)
+        sel = mask & (rng.random((N, gh, gw)) < 0.5)
         yp[sel, 0, 0:4] = yt[sel, 0:4] * (1 + 0.05 * rng.standard_normal((int(sel.sum()), 4))).astype(np.float32)
-        yp = yp.reshape(N, g, g, A * (5 + C))
+        yp = yp.reshape(N, gh, gw, A * (5 + C))
     return yt, yp
 
 
@@ -208,27 +210,30 @@ def test_metrics(version):
 
 
 @pytest.mark.parametrize("version,A,C,g,N", [(3, 3, 80, 13, 4), (3, 3, 80, 52, 2), (3, 3, 3, 8, 3), (4, 3, 80, 19, 2), (2, 5, 20, 13, 3),
-                                             (3, 3, 1, 5, 1), (3, 3, 91, 6, 2)])
+                                             (3, 3, 1, 5, 1), (3, 3, 91, 6, 2),
+                                             pytest.param(3, 3, 6, (13, 19), 3, id="3-3-6-13x19-3"),
+                                             pytest.param(3, 3, 80, (52, 20), 2, id="3-3-80-52x20-2")])
 def test_loss_cell_ahead_loader_equals_chunk_ahead_loader(version, A, C, g, N):
     """Round 6: the loss kernel requests a whole cell (its <= 256 prediction channels, class targets, true box, the anchors'
     predicted boxes) one cell ahead; yolo_set_option(8, 8) keeps the round-4 loader (one 64-channel chunk ahead). Same
     arithmetic on the same values in the same per-lane order: the gradient (v2 / v3) and the exported decisions must be
     BIT-identical, the loss parts equal up to the order of the per-workgroup fp64 atomics. (C = 91: 288 channels per cell, more than the
     cell-ahead loader holds -- the launcher keeps the old loader; one cell per wave and fewer cells than waves are covered by
-    the small grids.)"""
+    the small grids; g = (gh, gw): non-square grids, 13 x 19 = 247 cells.)"""
     from tf2_yolo_amd import ops
+    gh, gw = (g, g) if np.isscalar(g) else g
     anchors = ANCH9[:A] if A <= 9 else None
     if A == 5:
         anchors = [[0.75, 0.70], [0.60, 0.27], [0.25, 0.42], [0.14, 0.15], [0.04, 0.05]]
     yt, yp = make_case(N, g, A, C, anchors, seed=version * 100 + C)
     kw = dict(loss_weight=(1, 1, 5, 1)) if version != 4 else dict(loss_weight=(1, 5, 1), truth_thresh=0.7)
-    cfg = ops.make_loss_cfg(version, N, g, g, A, C, anchors=anchors, **kw)
+    cfg = ops.make_loss_cfg(version, N, gh, gw, A, C, anchors=anchors, **kw)
     ytd, ypd = torch.tensor(yt).cuda(), torch.tensor(yp).cuda()
     res = {}
     try:
         for opt in (8, 0):
             ops.set_option(8, opt)
-            dec = torch.full((N * g * g, 2), -7, dtype=torch.int32, device="cuda")
+            dec = torch.full((N * gh * gw, 2), -7, dtype=torch.int32, device="cuda")
             out, dp = ops.loss_fwd_bwd(cfg, ytd, ypd, decisions=dec)
             torch.cuda.synchronize()
             res[opt] = (out.cpu().numpy().copy(), dp.clone(), dec.clone())

@@ -24,8 +24,10 @@ A5 = [[0.75157846, 0.70525231], [0.60637077, 0.27136769], [0.25680231, 0.4211030
 
 
 def _labels(rng, N, g, C):
-    yt = np.zeros((N, g, g, 5 + C), dtype=np.float32)
-    mask = rng.random((N, g, g)) < 0.3
+    """g: the grid, one number for a square one or (gh, gw)"""
+    gh, gw = (g, g) if np.isscalar(g) else g
+    yt = np.zeros((N, gh, gw, 5 + C), dtype=np.float32)
+    mask = rng.random((N, gh, gw)) < 0.3
     mask[0, 0, 0] = True
     n = int(mask.sum())
     yt[mask, 0:2] = rng.random((n, 2))
@@ -138,9 +140,11 @@ A6 = A9[:6]
 HEADLINE_CLASSES = 80    # the full-batch headline tests (tests/test_gpu_fullsize.py, conftest.py) run the benchmark's C = 80
 
 
-def _setup(version, hw=None, N=2, unbiased=True, true_c1=False, tiny=False, class_num=None, ref_init=False):
+def _setup(version, hw=None, N=2, unbiased=True, true_c1=False, tiny=False, class_num=None, ref_init=False, shape=None):
     """class_num: YOLOv3 / YOLOv4 with that many classes instead of 3 (80 = what bench.py times: 255-channel heads, the
-    255 -> 256 padded head gradient, the C = 80 loss); ref_init: the reference's own YOLOv4 initialiser instead of he-normal"""
+    255 -> 256 padded head gradient, the C = 80 loss); ref_init: the reference's own YOLOv4 initialiser instead of he-normal;
+    shape = (H, W): a non-square input instead of hw x hw (YOLOv1.5: the input itself, not half of it) -- the facade gets
+    input_shape = (H, W, 3), and x, the label grids and the oracle's losses are sized by (gh, gw)"""
     import os
     rng = np.random.default_rng(version)
     names3 = ["a", "b", "c"] if class_num is None else [f"c{i}" for i in range(class_num)]
@@ -149,60 +153,65 @@ def _setup(version, hw=None, N=2, unbiased=True, true_c1=False, tiny=False, clas
     # well-conditioned fp32 problem at all (at 64x64 BOTH fp32 executions are O(1) off in the gradients)
     hw = hw or int(os.environ.get("TEST_MODEL_HW", "160" if version == 4 else "64"))
     g0 = hw // 32
+    inp = (hw, hw, 3) if shape is None else (shape[0], shape[1], 3)
+    gh0, gw0 = (g0, g0) if shape is None else (shape[0] // 32, shape[1] // 32)
     if version == 3 and tiny:
         # tiny-YOLOv3 (yolov3/models/darknet.py:107-135): two outputs (g0, 2 g0), six anchors, MaxPool(2, stride 1, same)
         import yolov3
-        y = yolov3.Yolo((hw, hw, 3), ["a", "b", "c"])
+        y = yolov3.Yolo(inp, ["a", "b", "c"])
         y.create_model(anchors=A6, backbone="tiny_darknet", pretrained_body=None, bn_unbiased_moving_var=unbiased)
         fwd = lambda w, x, tr, m=None: OM.yolov3_tiny_forward(w, x, A6, training=tr, leaky_masks=m,
                                                               unbiased_moving_var=unbiased)
-        loss_o = [OL.wrap_yolo_loss_v3((g0 * 2 ** i, g0 * 2 ** i), 3, 3, anchors=A6[3 * i:3 * i + 3],
+        loss_o = [OL.wrap_yolo_loss_v3((gh0 * 2 ** i, gw0 * 2 ** i), 3, 3, anchors=A6[3 * i:3 * i + 3],
                                        loss_weight=[1, 1, 5, 1]) for i in range(2)]
         loss_g = y.loss()
-        grids = [g0, 2 * g0]
+        grids = [(gh0, gw0), (2 * gh0, 2 * gw0)]
     elif version == 3:
         import yolov3
-        y = yolov3.Yolo((hw, hw, 3), names3)
+        y = yolov3.Yolo(inp, names3)
         y.create_model(anchors=A9, pretrained_body=None, bn_unbiased_moving_var=unbiased)
         fwd = lambda w, x, tr, m=None: OM.yolov3_forward(w, x, A9, training=tr, leaky_masks=m, unbiased_moving_var=unbiased)
-        loss_o = [OL.wrap_yolo_loss_v3((g0 * 2 ** i, g0 * 2 ** i), 3, C3, anchors=A9[3 * i:3 * i + 3],
+        loss_o = [OL.wrap_yolo_loss_v3((gh0 * 2 ** i, gw0 * 2 ** i), 3, C3, anchors=A9[3 * i:3 * i + 3],
                                        loss_weight=[1, 1, 5, 1]) for i in range(3)]
         loss_g = y.loss()
-        grids = [g0, 2 * g0, 4 * g0]
+        grids = [(gh0 * 2 ** i, gw0 * 2 ** i) for i in range(3)]
     elif version == 4:
         import yolov4
-        y = yolov4.Yolo((hw, hw, 3), names3)
+        y = yolov4.Yolo(inp, names3)
         y.create_model(anchors=A9, pretrained_body=None, bn_unbiased_moving_var=unbiased)
         fwd = lambda w, x, tr, m=None: OM.yolov4_forward(w, x, A9, training=tr, leaky_masks=m, unbiased_moving_var=unbiased)
-        loss_o = [OL.wrap_yolo_loss_v4((g0 * 2 ** i, g0 * 2 ** i), 3, C3, anchors=A9[3 * i:3 * i + 3],
+        loss_o = [OL.wrap_yolo_loss_v4((gh0 * 2 ** i, gw0 * 2 ** i), 3, C3, anchors=A9[3 * i:3 * i + 3],
                                        loss_weight=[1, 5, 1]) for i in range(3)]
         loss_g = y.loss()
-        grids = [g0, 2 * g0, 4 * g0]
+        grids = [(gh0 * 2 ** i, gw0 * 2 ** i) for i in range(3)]
     elif version == 2:
         import yolov2
-        y = yolov2.Yolo((hw, hw, 3), ["a", "b", "c", "d"])
+        y = yolov2.Yolo(inp, ["a", "b", "c", "d"])
         y.create_model(anchors=A5, bn_unbiased_moving_var=unbiased)
         fwd = lambda w, x, tr, m=None: OM.yolov2_forward(w, x, A5, training=tr, leaky_masks=m, unbiased_moving_var=unbiased)
-        loss_o = [OL.wrap_yolo_loss_v2((g0, g0), 5, 4, A5, loss_weight=[1, 1, 5, 1])]
+        loss_o = [OL.wrap_yolo_loss_v2((gh0, gw0), 5, 4, A5, loss_weight=[1, 1, 5, 1])]
         loss_g = [y.loss()]
-        grids = [g0]
+        grids = [(gh0, gw0)]
     else:
         import yolov1_5
         # true_c1: BASELINE.json config 1 at its real size: 224x224, ONE class, B = 2, grid 4x4
         names = ["raccoon"] if true_c1 else ["a", "b"]
-        y = yolov1_5.Yolo((2 * hw, 2 * hw, 3), names)
+        y = yolov1_5.Yolo((2 * hw, 2 * hw, 3) if shape is None else inp, names)
         y.create_model(bbox_num=2, bn_unbiased_moving_var=unbiased)
         if true_c1:
             g0 = y.grid_shape[0]      # 224 -> 112 -> 56 -> 28 -> 14 -> 7 -> ceil(7/2) = 4 (yolov1_5/__init__.py:91)
-        assert tuple(y.grid_shape) == (g0, g0)
+            gh0 = gw0 = g0
+        if shape is not None:         # five halvings, then the stride-2 'same' conv5_6: the input over 64
+            gh0, gw0 = shape[0] // 64, shape[1] // 64
+        assert tuple(y.grid_shape) == (gh0, gw0)
         fwd = lambda w, x, tr, m=None: OM.yolov1_5_forward(w, x, training=tr, leaky_masks=m, unbiased_moving_var=unbiased)
-        loss_o = [OL.wrap_yolo_loss_v1((g0, g0), 2, len(names), binary_weight=0.5, loss_weight=[5, 5, 1, 1])]
+        loss_o = [OL.wrap_yolo_loss_v1((gh0, gw0), 2, len(names), binary_weight=0.5, loss_weight=[5, 5, 1, 1])]
         loss_g = [y.loss(binary_weight=0.5)]
-        grids = [g0]
+        grids = [(gh0, gw0)]
     model = y.model
     (_reference_init if ref_init else _perturb)(model, rng)
-    H = y.input_shape[0]
-    x = rng.random((N, H, H, 3), dtype=np.float32)
+    H, W = y.input_shape[0], y.input_shape[1]
+    x = rng.random((N, H, W, 3), dtype=np.float32)
     ys = [_labels(rng, N, g, y.class_num) for g in grids]
     return y, model, fwd, loss_o, loss_g, x, ys
 
@@ -231,21 +240,22 @@ def _kink_census(version, y_true, pred_oracle, pred_dev, class_num):
     A pair is near a kink when one of the four corner differences truth - prediction, or one of the two overlap extents, is
     smaller in magnitude than the largest move the straight-through substitution makes to that pair's own box."""
     yt = torch.as_tensor(y_true, dtype=torch.float64)
-    g = yt.shape[1]
+    gh, gw = yt.shape[1], yt.shape[2]
+    g_wh = torch.tensor([gw, gh], dtype=torch.float64)
     if version == 1:
         B = (pred_oracle.shape[-1] - class_num) // 5
-        po = pred_oracle[..., :5 * B].reshape(-1, g, g, B, 5)[..., :4]
-        pd = pred_dev[..., :5 * B].reshape(-1, g, g, B, 5)[..., :4]
-        t = yt[..., :4].reshape(-1, g, g, 1, 4)
+        po = pred_oracle[..., :5 * B].reshape(-1, gh, gw, B, 5)[..., :4]
+        pd = pred_dev[..., :5 * B].reshape(-1, gh, gw, B, 5)[..., :4]
+        t = yt[..., :4].reshape(-1, gh, gw, 1, 4)
         obj = yt[..., 4] > 0
     else:
         B = pred_oracle.shape[-1] // (5 + class_num)
-        po = pred_oracle.reshape(-1, g, g, B, 5 + class_num)[..., :4]
-        pd = pred_dev.reshape(-1, g, g, B, 5 + class_num)[..., :4]
-        t = yt.reshape(-1, g, g, 1, 5 + class_num)[..., :4]
+        po = pred_oracle.reshape(-1, gh, gw, B, 5 + class_num)[..., :4]
+        pd = pred_dev.reshape(-1, gh, gw, B, 5 + class_num)[..., :4]
+        t = yt.reshape(-1, gh, gw, 1, 5 + class_num)[..., :4]
         obj = yt[..., 4] > 0
     def corners(b):
-        xy = b[..., 0:2] / g
+        xy = b[..., 0:2] / g_wh
         return xy - b[..., 2:4] / 2, xy + b[..., 2:4] / 2
     tmin, tmax = corners(t)
     pmin, pmax = corners(po)
@@ -257,18 +267,37 @@ def _kink_census(version, y_true, pred_oracle, pred_dev, class_num):
     return int((dist[sel] <= move[sel]).sum()), int(sel.sum())
 
 
+# true_c1 tag -> ((H, W), the output grids (gh, gw) coarse -> fine) of the non-square cases
+NONSQUARE = {"64x96": ((64, 96), [(2, 3), (4, 6), (8, 12)]), "96x64": ((96, 64), [(3, 2), (6, 4), (12, 8)]),
+             "tiny96x160": ((96, 160), [(3, 5), (6, 10)]), "160x96": ((160, 96), [(5, 3), (10, 6), (20, 12)]),
+             "128x192": ((128, 192), [(2, 3)])}
+
+
 # (version, BN moving variance fed Bessel-corrected [tf.keras fused BN, the default] or biased, C1 at its true size)
 @pytest.mark.parametrize("version,unbiased,true_c1", [(3, True, False), (2, True, False), (1, True, False), (4, True, False),
                                                       (3, False, False), (1, True, True), (3, True, "tiny"),
                                                       (3, True, "416"), (4, True, "608"), (2, True, "416"),
                                                       (3, True, "tiny416"), (4, True, "608bs1"),
                                                       (3, True, "416c80bs8"), (4, True, "608refinit"),
-                                                      (3, True, "416c80bs32"), (4, True, "608c80bs4")])
+                                                      (3, True, "416c80bs32"), (4, True, "608c80bs4"),
+                                                      (3, True, "64x96"), (3, True, "96x64"), (3, True, "tiny96x160"),
+                                                      (4, True, "160x96"), (2, True, "96x64"), (1, True, "128x192")])
 def test_model_parity(version, unbiased, true_c1):
     from tf2_yolo_amd import optimizers
     import conftest
     conftest.foreground_threads()     # explicit CPU threads for this test's oracle passes (half the box while conftest's jobs run)
-    if true_c1 == "tiny416":   # tiny-YOLOv3 at its usual resolution: 416x416, grids 13 and 26 (bs 2)
+    if true_c1 in NONSQUARE:
+        # H != W (bs 2): every pyramid level has distinct gh, gw. tiny-YOLOv3 runs the stride-1 'same' pool on a 3 x 5 map,
+        # YOLOv4 SPP 5 / 9 / 13 on a 5 x 3 map and the plane pool kernels, YOLOv2 the space-to-depth passthrough
+        shape, want = NONSQUARE[true_c1]
+        y, model, fwd, loss_o, loss_g, x, ys = _setup(version, N=2, unbiased=unbiased, tiny=true_c1.startswith("tiny"), shape=shape)
+        outs_ = model.output if isinstance(model.output, (list, tuple)) else [model.output]
+        assert x.shape == (2, shape[0], shape[1], 3) and tuple(y.input_shape) == (shape[0], shape[1], 3)
+        want = want[:len(outs_)]                                            # (YOLOv2 at 96 x 64: the 3 x 2 grid alone)
+        assert sorted(tuple(o.shape[1:3]) for o in outs_) == want          # (gh, gw, ...), not transposed
+        assert [tuple(o.shape[1:3]) for o in outs_] == [tuple(a.shape[1:3]) for a in ys]
+        assert tuple(y.grid_shape) == want[0] == tuple(outs_[0].shape[1:3])
+    elif true_c1 == "tiny416":   # tiny-YOLOv3 at its usual resolution: 416x416, grids 13 and 26 (bs 2)
         y, model, fwd, loss_o, loss_g, x, ys = _setup(3, hw=416, N=2, unbiased=unbiased, tiny=True)
         assert [tuple(o.shape[1:3]) for o in model.output] == [(13, 13), (26, 26)]
     elif true_c1 == "tiny":   # tiny-YOLOv3 at 96x96: grids 3 and 6, the stride-1 'same' max-pool on a 3x3 map
@@ -545,6 +574,79 @@ def test_model_parity(version, unbiased, true_c1):
     lr_t = lr * np.sqrt(1 - b2) / (1 - b1)
     expect = p_before.double() - lr_t * m / (v.sqrt() + eps)
     assert (net.params.data.double() - expect).abs().max().item() < 1e-6
+
+
+@pytest.mark.parametrize("env", [{}, {"YOLO_INFER_SMALL_FUSE": "0"}], ids=lambda e: " ".join(f"{k}={v}" for k, v in e.items()) or "default")
+@pytest.mark.parametrize("version,shape", [(3, (64, 96)), (4, (160, 96))], ids=["v3-64x96", "v4-160x96"])
+def test_nonsquare_predict_decode_nms(version, shape, env, monkeypatch):
+    """Model.predict at bs 1 on a non-square input -- the small-tile and head-unit dispatch, the Concatenate that reads
+    through UpSampling2D, the SPP pools inside the captured graph -- against the float64 oracle's inference forward at this
+    file's forward tolerance; a second image and then the first again replay the graph. Then decode + nms + soft_nms on the
+    device's own prediction, bit for bit against oracle/tools.py (tests/test_gpu_infer_bs1.py does this at 416 x 416).
+    Weights: labels.synthetic_keras_weights with residual gamma 0.1, the recipe of that file (inference-mode statistics)."""
+    import yolov3, yolov4
+    from oracle import tools as T
+    from tf2_yolo_amd import graphs, labels, tools
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    H, W = shape
+    names = ["a", "b", "c"]
+    if version == 3:
+        y = yolov3.Yolo((H, W, 3), names)
+        y.create_model(anchors=A9, pretrained_body=None)
+        w = labels.synthetic_keras_weights(graphs.build_yolov3((H, W, 3), 3), 77, residual_gamma=0.1)
+        fwd = lambda wt, xt: OM.yolov3_forward(wt, xt, A9, training=False)[0]
+    else:
+        y = yolov4.Yolo((H, W, 3), names)
+        y.create_model(anchors=A9, pretrained_body=None)
+        w = labels.synthetic_keras_weights(graphs.build_yolov4((H, W, 3), 3), 77, residual_gamma=0.1)
+        fwd = lambda wt, xt: OM.yolov4_forward(wt, xt, A9, training=False)[0]
+    model = y.model
+    net = model.net
+    assert bool(net._infer_small_fuse) == (not env)
+    for n in model.layer_names():
+        lay = model.get_layer(n)
+        k = len(lay.get_weights())
+        if k and not n.endswith("_anchor"):
+            lay.set_weights([w[f"{n}/{i}"] for i in range(k)])
+    rng = np.random.default_rng(5)
+    x1, x2 = (rng.random((1, H, W, 3), dtype=np.float32) for _ in range(2))
+    gh, gw = H // 32, W // 32
+    assert sorted(tuple(o.shape[1:3]) for o in model.output) == [(gh, gw), (2 * gh, 2 * gw), (4 * gh, 4 * gw)]
+
+    def oracle(x, dtype):
+        with torch.no_grad():
+            return [o.numpy() for o in fwd({k: torch.tensor(v, dtype=dtype) for k, v in w.items()}, torch.tensor(x, dtype=dtype))]
+    p1 = model.predict(x1, batch_size=1)
+    assert net._use_infer_graph and 1 in net._infer_graphs
+    p2 = model.predict(x2, batch_size=1)
+    p1b = model.predict(x1, batch_size=1)
+    for a, b in zip(p1, p1b):
+        assert np.array_equal(a, b)
+    for x, pred in ((x1, p1), (x2, p2)):
+        o64, o32 = oracle(x, torch.float64), oracle(x, torch.float32)
+        floor = max(_rel(a, b) for a, b in zip(o32, o64))
+        errs = []
+        for a, b in zip(pred, o64):
+            assert a.shape == b.shape and np.isfinite(a).all()
+            errs.append(float(_rel(a, b)))
+        log_parity_ratio({"case": f"v{version} {H}x{W} bs1 predict {env or 'default'}", "fp32_floor": float(floor), "forward_err": max(errs),
+                          "forward_ratio": max(errs) / max(floor, 1e-30)})
+        assert max(errs) < max(1e-4, 1.5 * floor), (errs, floor)
+    assert min(_rel(a, b) for a, b in zip(p2, p1)) > 1e-3           # (the second image gave another prediction)
+    # decode and NMS on the device's own prediction: levels fine -> coarse (by cell count), conf x prob >= 0.25; NMS at 0.3
+    # (at 0.5 nothing is suppressed among these candidates)
+    lv = [p[0] for p in sorted(p1, key=lambda p: -p.shape[1] * p.shape[2])]
+    dec = tools.decode_device(*[torch.from_numpy(a).cuda() for a in lv], class_num=3, threshold=0.25, version=3).cpu().numpy()
+    ref = T.decode(*lv, class_num=3, threshold=0.25, version=3)
+    assert dec.shape[0] > 100 and np.array_equal(dec, ref)
+    kept = T.nms(ref, 3, 0.3)
+    print("nonsquare predict: candidates", dec.shape[0], "kept", kept.shape[0])
+    assert 0 < kept.shape[0] < dec.shape[0]
+    assert np.array_equal(tools.nms(dec, class_num=3, nms_threshold=0.3), kept)
+    assert np.array_equal(tools.nms(dec, class_num=3, nms_threshold=0.3, iou_mode=2), T.nms(ref, 3, 0.3, 2))
+    assert np.array_equal(tools.soft_nms(dec, class_num=3, nms_threshold=0.3, conf_threshold=0.25, sigma=0.5),
+                          T.soft_nms(ref, 3, 0.3, 0.25, 0.5))
 
 
 def _grad_view(model, lname, idx, flat):

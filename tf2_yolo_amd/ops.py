@@ -206,7 +206,8 @@ def ensure_wgrad_workspace():
 # profiles/r04_b_dp_*): with RCCL initialised first, the filter-gradient stream -- created lazily in the first forward pass --
 # landed on the compute stream's queue: 34.2 instead of 30.1 ms per step; as the fourth model of one process, YOLOv4-608's own
 # filter-gradient stream did the same: 58.8 instead of 39.7 ms. So the process has ONE stream per role, shared by every model,
-# and the roles are created together, filter gradients first: call create_side_streams() before anything else creates streams
+# and the roles are created together, filter gradients first, and each is used once right away (_first_use: the queue is bound
+# at a stream's first use): call create_side_streams() before anything else creates streams
 # (bench.py does, before init_process_group; Network.__init__ does for single-process use). YOLO_STREAM_PROBE=1 additionally
 # checks with two spin kernels that the new stream overlaps the current one and warns if not (diagnostic; the probe's extra
 # streams shift later assignments, so it is off by default).
@@ -235,6 +236,19 @@ def _overlaps(a, b, cycles=6000000):   # ~3 ms per spin kernel: far above the ~5
     return e0.elapsed_time(e2) < 1.5 * one
 
 
+def _first_use(st, dev):
+    """The runtime gives a stream its hardware queue when the stream is first USED, not when it is created: with the default
+    of 4 queues, side streams that were created early but first used in the first backward pass -- behind RCCL's streams --
+    still landed on the compute stream's queue in a data-parallel rank (33.9 instead of 29.8 ms per step at 4 queues; 30.3 /
+    30.1 ms at 2 / 8; 30.1 ms at 4 once the streams had run anything early). So the compute stream and then the new stream
+    each run one tiny fill here, in creation order."""
+    with torch.cuda.device(dev):
+        torch.zeros(1, device=f"cuda:{dev}")
+        with torch.cuda.stream(st):
+            torch.zeros(1, device=f"cuda:{dev}")
+        torch.cuda.current_stream().wait_stream(st)
+
+
 def create_side_streams(device=None):
     """the filter-gradient and communication streams of `device` (default: the current device), in that order (idempotent;
     one pair per device of the process, created on that device explicitly)"""
@@ -250,6 +264,7 @@ def create_side_streams(device=None):
                 warnings.warn(f"tf2_yolo_amd: the {role} stream shares a hardware queue with the compute stream: the step "
                               "will run them one after the other (create_side_streams() earlier, or raise GPU_MAX_HW_QUEUES)")
             _SIDE_STREAMS[(dev, role)] = st
+            _first_use(st, dev)
     return {role: _SIDE_STREAMS[(dev, role)] for role in ("wgrad", "comm")}
 
 
