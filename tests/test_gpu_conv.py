@@ -1224,6 +1224,12 @@ def test_conv_wgrad_window_kernel(case, variant):
         ops.reset_options()
 
 
+def test_conv_wgrad_window_kernel_reads_two_steps_ahead():
+    """variant 2 of the kernel above (fragment reads two tap-steps ahead; the 256-slot ring only): the same checks on the
+    smallest of its cases"""
+    test_conv_wgrad_window_kernel(WGRAD_WIN_CASES[2], 2)
+
+
 def test_batched_filter_split_equals_per_tensor_split():
     """yolo_split_planes_batch / yolo_filter_transpose_batch (one launch for every filter of a network) against the
     per-tensor entry points, byte for byte: ragged row counts, a job smaller than one workgroup, and a transposed

@@ -232,3 +232,39 @@ def test_header_is_plain_c_and_a_c_host_links_the_library(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.stdout, r.stderr)
     assert "abi 5" in r.stdout and "bad args" in r.stdout
+
+
+def test_env_knob_helpers(tmp_path):
+    """env_int / env_ll (csrc/env.hpp), the one reader of the YOLO_* tuning knobs: unset gives the default, anything else
+    atoi / atoll of the text (so "" and "abc" give 0, and "0" switches a default-on knob off); env_ll keeps values above
+    2^31. A stand-alone host program: no HIP header, no GPU."""
+    import subprocess
+    src = tmp_path / "env_check.cpp"
+    src.write_text(r'''
+#include "env.hpp"
+#include <cstdio>
+#define CHECK(c) do { if (!(c)) { std::printf("FAILED: %s\n", #c); return 1; } } while (0)
+int main() {
+  using yolo::env_int;
+  using yolo::env_ll;
+  unsetenv("YOLO_T");
+  CHECK(env_int("YOLO_T", 7) == 7 && env_int("YOLO_T", -1) == -1 && env_ll("YOLO_T", 5000000000LL) == 5000000000LL);
+  const struct { const char* text; int want; } cases[] = {{"0", 0}, {"", 0}, {"abc", 0}, {"-3", -3}, {"8", 8}};
+  for (const auto& c : cases) {
+    setenv("YOLO_T", c.text, 1);
+    CHECK(env_int("YOLO_T", 7) == c.want);
+    CHECK(env_ll("YOLO_T", 7) == c.want);
+    CHECK((env_int("YOLO_T", 1) != 0) == (c.want != 0));   // the on / off knobs
+  }
+  setenv("YOLO_T", "6442450944", 1);   // 3 * 2^31
+  CHECK(env_ll("YOLO_T", 0) == 6442450944LL);
+  std::puts("ok");
+  return 0;
+}
+''')
+    exe = str(tmp_path / "env_check")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "tf2_yolo_amd", "csrc"), str(src),
+                        "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", (r.stdout, r.stderr)

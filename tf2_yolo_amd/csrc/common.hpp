@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstdint>
 #include "../../include/yolo_hip.h"
+#include "env.hpp"
 
 namespace yolo {
 
@@ -17,6 +18,44 @@ inline int check_launch(const char* what) {
     return YOLO_ERR_LAUNCH;
   }
   return YOLO_OK;
+}
+
+// ---- kernels with more dynamic LDS than the default 64 KB limit ----
+// Kernel = the address of one kernel instantiation, named once per form. What these helpers learn is cached per process in
+// function-local statics, not per device: ops.ensure_conv_workspace refuses a second device in one process.
+
+// Raises Kernel's dynamic-LDS limit at first use; false (and the error text says why) when the runtime refused.
+template <auto Kernel, size_t LDS_BYTES>
+inline bool lds_limit_ok(const char* what) {
+  static const hipError_t err =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_BYTES);
+  if (err != hipSuccess)
+    set_error("%s: raising the dynamic LDS limit to %zu bytes failed: %s", what, (size_t)LDS_BYTES, hipGetErrorString(err));
+  return err == hipSuccess;
+}
+
+template <auto Kernel, size_t LDS_BYTES, class Args>
+inline int launch_lds(dim3 grid, dim3 block, hipStream_t st, const Args& args, const char* what) {
+  if (!lds_limit_ok<Kernel, LDS_BYTES>(what)) return YOLO_ERR_LAUNCH;
+  hipLaunchKernelGGL(Kernel, grid, block, LDS_BYTES, st, args);
+  return check_launch(what);
+}
+
+// Workgroups of Kernel the chip holds at once (occupancy x CUs), asked once, after the limit is raised; 0 = a query failed
+// (the call site has its own fallback).
+template <auto Kernel, size_t LDS_BYTES>
+inline int resident_workgroups(int block_threads, const char* what) {
+  if (!lds_limit_ok<Kernel, LDS_BYTES>(what)) return 0;
+  static const int resident = [block_threads] {
+    int per_cu = 0, dev = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(Kernel), block_threads, LDS_BYTES) ==
+            hipSuccess &&
+        hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        per_cu > 0 && cus > 0)
+      return per_cu * cus;
+    return 0;
+  }();
+  return resident;
 }
 
 #define YOLO_REQUIRE(cond, ...)            \

@@ -355,14 +355,7 @@ static int launch_gather(GatherConvArgs& a, hipStream_t st) {
   }
   a.nblocks = (int)nb;
   constexpr size_t lds = 2 * (BM + BN) * 36 * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_kernel<BM, BN, WGM, WGN, FLAT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gather_conv_kernel<BM, BN, WGM, WGN, FLAT>), dim3((unsigned)nb), dim3(256), lds, st, a);
-  return check_launch("gather_conv_kernel");
+  return launch_lds<gather_conv_kernel<BM, BN, WGM, WGN, FLAT>, lds>(dim3((unsigned)nb), dim3(256), st, a, "gather_conv_kernel");
 }
 
 // 0 = exact-fp32 MFMA kernels (this file), 1 = fp32 emulated with 6 bf16 MFMA passes (conv_split.hip)
@@ -384,7 +377,7 @@ static int dispatch_gather(GatherConvArgs& a, bool flat, hipStream_t st) {
   if (a.Cout <= 64) return launch_gather<128, 64, 2, 2, false>(a, st);
   // Wide outputs: 128x128 tiles unless the grid would not even fill the 256 CUs x 2 workgroups once;
   // then 64-row tiles (twice the blocks) balance the chip: 13x13 / 26x26 layers gain 10-15 %.
-  static const int force = [] { const char* e = getenv("YOLO_CONV_TILE_M"); return e ? atoi(e) : 0; }();
+  static const int force = env_int("YOLO_CONV_TILE_M", 0);
   const long long blocks128 = ((a.M + 127) / 128) * ((a.Cout + 127) / 128);
   bool use64 = false;
   if (force == 64) use64 = true;
@@ -705,7 +698,7 @@ static int launch_wgrad(WgradArgs& a, hipStream_t st) {
   // stem of YOLOv1.5 and every layer whose channel counts keep it off the planes kernels took this path, and its
   // gradients differed in the last bit from run to run (scripts/step_repro.py c1)
   a.slabs = nullptr;
-  static const bool det_env = [] { const char* e = getenv("YOLO_WGRAD_DETERMINISTIC"); return !(e && atoi(e) == 0); }();
+  static const bool det_env = env_int("YOLO_WGRAD_DETERMINISTIC", 1) != 0;
   size_t ws_bytes = 0;
   unsigned char* ws = reinterpret_cast<unsigned char*>(wgrad_workspace(&ws_bytes));
   if (det_env && ws != nullptr && ws_bytes > WGRAD_WS_COLSUM_BYTES) {
@@ -1176,7 +1169,7 @@ static int dgrad_impl(const yolo_conv_desc* d, const float* dy, const float* wT,
                "conv_dgrad: Cout %% 32 != 0 only supported for 1x1 stride-1 (head) convs");
   // planes kernels, stride 2: ONE launch for the four parity classes (each class alone re-streams all of dy: 354 MB four
   // times for the 416 -> 208 layer at bs 32). YOLO_DGRAD_CLASSES=0: one launch per class, as the fp32 kernels do.
-  static const bool fuse_classes = [] { const char* e = getenv("YOLO_DGRAD_CLASSES"); return !(e && atoi(e) == 0); }();
+  static const bool fuse_classes = env_int("YOLO_DGRAD_CLASSES", 1) != 0;
   if (planes && fuse_classes && d->sh * d->sw > 1 && d->sh * d->sw <= 4) {
     GatherConvArgs a{};
     a.src = dy;

@@ -280,7 +280,14 @@ __global__ __launch_bounds__(256) void split_planes_padded_kernel(const float* _
 //   read fragments of stage kt+1 into the other register set
 //   3 MFMA passes per fragment pair on stage kt's registers, with the 2 DMAs of stage kt+3 (into stage
 //   kt's buffer) issued between them
-template <int BM, int BN, int WGM, int WGN, int DBG = 0>
+// FORM: which kernel this instantiation is. The values are part of every kernel's symbol name.
+constexpr int PF_KO_MASK = 31;   // diagnostic knock-outs of the main loop (wrong results; launch_gather_planes: YOLO_PLANES_DBG)
+constexpr int PF_SPLIT = 32;     // split-K: accumulators go to a slab
+constexpr int PF_MULTI = 64;     // the parity classes of a strided data gradient in one launch
+constexpr int PF_DEEP1 = 128;    // one more DMA stage in the ring
+constexpr int PF_DEEP2 = 256;    // two more
+constexpr int PF_BNRED = 512;    // the fused BatchNorm-backward reduction
+template <int BM, int BN, int WGM, int WGN, int FORM = 0>
 __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gather_conv_planes_kernel(const GatherConvArgs a) {
   constexpr int NW = WGM * WGN;
   constexpr int TM = BM / WGM / 32;
@@ -293,7 +300,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
   static_assert(LPW <= 4, "loader layout: slot s = wave + i*NW loads A block s, or B block (s - RBA) % RBB");
   constexpr int ND = PL_PLANES * LPW;   // DMA instructions per wave per stage
   constexpr int STAGE_BYTES = (RBA + RBB) * PL_PLANES * 1024;
-  constexpr int NBUF = 3 + ((DBG >> 7) & 3);   // (bits 128 / 256: a deeper ring, NBUF - 1 stages in flight -- HBM-bound 1x1 layers)
+  constexpr int NBUF = 3 + ((FORM >> 7) & 3);   // (PF_DEEP1 / PF_DEEP2: a deeper ring, NBUF - 1 stages in flight -- HBM-bound 1x1 layers)
 
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned lds_base = (unsigned)(size_t)smem;
@@ -305,15 +312,15 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
 
   // split-K (a.split_parts > 1, conv_win.hip: conv_split_reduce_kernel): grid = tiles x parts, part p of a tile
   // contracts the 16-channel blocks [p * cpt / P, (p + 1) * cpt / P) of every tap and stores its accumulators to a slab
-  // (its own instantiation, DBG bit 32: inside the production kernel the slab path cost 44 registers = one wave per SIMD)
-  constexpr bool SPLIT = (DBG & 32) != 0;
+  // (its own instantiation, PF_SPLIT: inside the production kernel the slab path cost 44 registers = one wave per SIMD)
+  constexpr bool SPLIT = (FORM & PF_SPLIT) != 0;
   const int SP = SPLIT ? a.split_parts : 1;
   const int part = SPLIT ? (int)blockIdx.x / a.nblocks : 0;
   const int tile = xcd_remap(SPLIT ? (int)blockIdx.x - part * a.nblocks : (int)blockIdx.x, a.nblocks);
-  // multi-class launch (its own instantiation, DBG bit 64; a.ncls parity classes of a strided data gradient): tile =
+  // multi-class launch (its own instantiation, PF_MULTI; a.ncls parity classes of a strided data gradient): tile =
   // (row tile, class, column tile); everything that depends on the output grid comes from the class
-  constexpr bool MULTI = (DBG & 64) != 0;
-  constexpr bool BNRED = (DBG & 512) != 0;   // the fused BatchNorm-backward reduction (planes_epilogue.hpp): its own kernels
+  constexpr bool MULTI = (FORM & PF_MULTI) != 0;
+  constexpr bool BNRED = (FORM & PF_BNRED) != 0;   // the fused BatchNorm-backward reduction (planes_epilogue.hpp): its own kernels
   const int tile_n = tile % a.tiles_n;
   const int cls = MULTI ? (tile / a.tiles_n) % a.ncls : 0;
   const int tile_m = MULTI ? tile / (a.tiles_n * a.ncls) : tile / a.tiles_n;
@@ -460,13 +467,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          if constexpr (!(DBG & 8)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[S][pa][i], fb[S][pb][j], acc[i][j], 0, 0, 0);
+          if constexpr (!(FORM & 8)) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[S][pa][i], fb[S][pb][j], acc[i][j], 0, 0, 0);
           const int idx = (q * TM + i) * TN + j;
 #pragma unroll
           for (int d = 0; d < ND; ++d)
             if (idx == (((d + 1) * NM) / (ND + 1) > 0 ? ((d + 1) * NM) / (ND + 1) - 1 : 0)) {
               __builtin_amdgcn_sched_barrier(0);
-              if constexpr (!(DBG & 1)) issue_plane(d, wbuf);
+              if constexpr (!(FORM & 1)) issue_plane(d, wbuf);
               __builtin_amdgcn_sched_barrier(0);
             }
         }
@@ -492,8 +499,8 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
     // my pieces of stage kt+1 have landed (those of kt+2 may still fly)
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * ND) : "memory");
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // my reads of stage kt's buffer are done
-    if constexpr (!(DBG & 4)) __builtin_amdgcn_s_barrier();
-    if constexpr (!(DBG & 2)) read_frags(rbuf, NXT);
+    if constexpr (!(FORM & 4)) __builtin_amdgcn_s_barrier();
+    if constexpr (!(FORM & 2)) read_frags(rbuf, NXT);
     __builtin_amdgcn_sched_barrier(0);
     mfma_stage(CUR, wbuf);
   };
@@ -518,10 +525,10 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
   else if constexpr (MULTI)
     planes_epilogue<BM, BN, WGM, WGN, NBUF * STAGE_BYTES, 0, NoStamp, false, BNRED>(a, acc, smem, m0, n0, tile_m, wm, wn, lane, tid, NoStamp(), &G);
   else
-    planes_epilogue<BM, BN, WGM, WGN, NBUF * STAGE_BYTES, (DBG & 31), NoStamp, false, BNRED>(a, acc, smem, m0, n0, tile_m, wm, wn, lane, tid);
+    planes_epilogue<BM, BN, WGM, WGN, NBUF * STAGE_BYTES, (FORM & PF_KO_MASK), NoStamp, false, BNRED>(a, acc, smem, m0, n0, tile_m, wm, wn, lane, tid);
 }
 
-template <int BM, int BN, int WGM, int WGN, int DBG = 0>
+template <int BM, int BN, int WGM, int WGN, int FORM = 0>
 static int launch_planes(GatherConvArgs& a, hipStream_t st) {
   const long long tiles_m = (a.M + BM - 1) / BM;
   a.tiles_n = (a.Cout + BN - 1) / BN;
@@ -530,8 +537,9 @@ static int launch_planes(GatherConvArgs& a, hipStream_t st) {
     set_error("conv(planes): bad grid %lld", nb);
     return YOLO_ERR_INVALID_ARG;
   }
-  constexpr size_t lds = (3 + ((DBG >> 7) & 3)) * (BM / 32 + BN / 32) * PL_PLANES * 1024;
-  if constexpr (DBG == 0) {
+  constexpr size_t lds = (3 + ((FORM >> 7) & 3)) * (BM / 32 + BN / 32) * PL_PLANES * 1024;
+  const dim3 block(64 * WGM * WGN);
+  if constexpr (FORM == 0) {
     if (a.ncls > 1) {   // the parity classes of a strided data gradient in one launch
       long long tm = 0;
       for (int c = 0; c < a.ncls; ++c) tm = std::max(tm, (a.cls[c].M + BM - 1) / BM);
@@ -544,71 +552,39 @@ static int launch_planes(GatherConvArgs& a, hipStream_t st) {
       a.split_parts = 1;
       a.bwd_nslots = (int)(tm * a.ncls);
       YOLO_BNRED_CHECK(a)
-      static bool attr64 = false;
-      if (!attr64) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_planes_kernel<BM, BN, WGM, WGN, 64>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr64 = true;
-      }
-      if (a.bwd_y != nullptr) {
-        static bool attr576 = false;
-        if (!attr576) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_planes_kernel<BM, BN, WGM, WGN, 64 | 512>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-          attr576 = true;
-        }
-        hipLaunchKernelGGL((gather_conv_planes_kernel<BM, BN, WGM, WGN, 64 | 512>), dim3((unsigned)nbm), dim3(64 * WGM * WGN), lds, st, a);
-        return check_launch("gather_conv_planes_kernel(classes, bn reduce)");
-      }
-      hipLaunchKernelGGL((gather_conv_planes_kernel<BM, BN, WGM, WGN, 64>), dim3((unsigned)nbm), dim3(64 * WGM * WGN), lds, st, a);
-      return check_launch("gather_conv_planes_kernel(classes)");
+      if (a.bwd_y == nullptr)
+        return launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, PF_MULTI>, lds>(dim3((unsigned)nbm), block, st, a,
+                                                                                      "gather_conv_planes_kernel(classes)");
+      return launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, PF_MULTI | PF_BNRED>, lds>(
+          dim3((unsigned)nbm), block, st, a, "gather_conv_planes_kernel(classes, bn reduce)");
     }
   }
   a.nblocks = (int)nb;
   a.bwd_nslots = (int)tiles_m;
   YOLO_BNRED_CHECK(a)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_planes_kernel<BM, BN, WGM, WGN, DBG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
+  constexpr auto plain = &gather_conv_planes_kernel<BM, BN, WGM, WGN, FORM>;   // (beside it: its split-K and BatchNorm-reduction forms)
   a.split_parts = 1;
-  if constexpr (BM == 128 && BN == 128 && WGM == 2 && WGN == 2 && DBG == 0) {
+  if constexpr (BM == 128 && BN == 128 && WGM == 2 && WGN == 2 && FORM == 0) {
     // at least 8 stages per part (a.kc = the whole channel range in one chunk is the default stage order)
     const int min_cb = a.ntaps >= 8 ? 1 : (8 + a.ntaps - 1) / a.ntaps;
     a.split_parts = conv_split_parts(a, nb, BM, min_cb, 4);
     if (a.split_parts > 1) {
       a.sk_slabs = conv_split_slabs();
-      static bool attr32 = false;
-      if (!attr32) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_planes_kernel<BM, BN, WGM, WGN, 32>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr32 = true;
-      }
-      hipLaunchKernelGGL((gather_conv_planes_kernel<BM, BN, WGM, WGN, 32>), dim3((unsigned)(nb * a.split_parts)),
-                         dim3(64 * WGM * WGN), lds, st, a);
-      if (int rc = check_launch("gather_conv_planes_kernel(split)")) return rc;
+      if (int rc = launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, PF_SPLIT>, lds>(
+              dim3((unsigned)(nb * a.split_parts)), block, st, a, "gather_conv_planes_kernel(split)"))
+        return rc;
       return launch_split_reduce(a, BM, st);
     }
   }
-  if constexpr ((DBG & ~(128 | 256)) == 0) {
-    if (a.bwd_y != nullptr) {
-      static bool attr_bn = false;
-      if (!attr_bn) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_planes_kernel<BM, BN, WGM, WGN, DBG | 512>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_bn = true;
-      }
-      hipLaunchKernelGGL((gather_conv_planes_kernel<BM, BN, WGM, WGN, DBG | 512>), dim3((unsigned)nb), dim3(64 * WGM * WGN), lds, st, a);
-      return check_launch("gather_conv_planes_kernel(bn reduce)");
-    }
+  if constexpr ((FORM & ~(PF_DEEP1 | PF_DEEP2)) == 0) {
+    if (a.bwd_y != nullptr)
+      return launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, FORM | PF_BNRED>, lds>(dim3((unsigned)nb), block, st, a,
+                                                                                          "gather_conv_planes_kernel(bn reduce)");
   } else if (a.bwd_y != nullptr) {
     set_error("conv(planes): this diagnostic instantiation has no fused BatchNorm-backward reduction");
     return YOLO_ERR_INVALID_ARG;
   }
-  hipLaunchKernelGGL((gather_conv_planes_kernel<BM, BN, WGM, WGN, DBG>), dim3((unsigned)nb), dim3(64 * WGM * WGN), lds, st, a);
-  return check_launch("gather_conv_planes_kernel");
+  return launch_lds<plain, lds>(dim3((unsigned)nb), block, st, a, "gather_conv_planes_kernel");
 }
 
 long long planes_bytes(long long rows, int C) { return planes_body_bytes(rows, C) + PL_HEADER; }
@@ -626,16 +602,16 @@ int launch_gather_planes(GatherConvArgs& a, hipStream_t st) {
   a.wgt_bytes = (unsigned)bytesB;
   a.zero_blk_src = (int)((rowsA + 15) / 16);
   a.zero_blk_wgt = (a.Cout + 15) / 16;
-  static const int nt = [] { const char* e = getenv("YOLO_NT_STORE"); return e ? atoi(e) : 1; }();
+  static const int nt = env_int("YOLO_NT_STORE", 1);
   a.nt_store = nt;
-  static const int vecst = [] { const char* e = getenv("YOLO_VEC_STORE"); return e ? atoi(e) : 1; }();
+  static const int vecst = env_int("YOLO_VEC_STORE", 1);
   // (the wave-private staging of planes_epilogue.hpp has no workgroup barriers: used at every size)
   a.vec_store = vecst;
   // diagnostic knock-outs of the main loop (wrong results): 1 no DMA, 2 no fragment reads, 4 no barrier, 8 no MFMA, 16 no output stores
-  static const int dbg = [] { const char* e = getenv("YOLO_PLANES_DBG"); return e ? atoi(e) : 0; }();
+  static const int dbg = env_int("YOLO_PLANES_DBG", 0);
   a.dbg = dbg;
   // channel-block chunk of the stage order (see the kernel): YOLO_PLANES_KC overrides
-  static const int kc_env = [] { const char* e = getenv("YOLO_PLANES_KC"); return e ? atoi(e) : 0; }();
+  static const int kc_env = env_int("YOLO_PLANES_KC", 0);
   a.kc = kc_env > 0 ? kc_env : (a.Cs >> 4);
   if (a.kc > (a.Cs >> 4)) a.kc = a.Cs >> 4;
   // 3x3 stride-1 forward / data gradient: the kernel that keeps the input window in LDS (conv_win.hip)
@@ -649,22 +625,22 @@ int launch_gather_planes(GatherConvArgs& a, hipStream_t st) {
   // number of bytes in flight, so their DMA ring is deeper -- 5 stages (4 in flight, 80 KB, two workgroups per CU) under
   // the 128 x 128 tile, 4 under the narrower ones (a fifth costs them a resident workgroup). Same-box A/B of the whole
   // step: C3 30.81 -> 30.63 ms, C4 41.35 -> 40.84 ms. YOLO_PLANES_DEEP = 0 / 1 / 2 forces the number of extra stages.
-  static const int deep_env = [] { const char* e = getenv("YOLO_PLANES_DEEP"); return e ? atoi(e) : -1; }();
+  static const int deep_env = env_int("YOLO_PLANES_DEEP", -1);
   const int deep = deep_env >= 0 ? deep_env : (a.Cout <= 64 ? 1 : 2);
   if (deep && a.ntaps == 1 && a.ncls <= 1) {
-    if (a.Cout <= 32) return deep == 1 ? launch_planes<128, 32, 4, 1, 128>(a, st) : launch_planes<128, 32, 4, 1, 256>(a, st);
-    if (a.Cout <= 64) return deep == 1 ? launch_planes<128, 64, 4, 2, 128>(a, st) : launch_planes<128, 64, 4, 2, 256>(a, st);
+    if (a.Cout <= 32) return deep == 1 ? launch_planes<128, 32, 4, 1, PF_DEEP1>(a, st) : launch_planes<128, 32, 4, 1, PF_DEEP2>(a, st);
+    if (a.Cout <= 64) return deep == 1 ? launch_planes<128, 64, 4, 2, PF_DEEP1>(a, st) : launch_planes<128, 64, 4, 2, PF_DEEP2>(a, st);
   }
   if (a.Cout <= 32) return launch_planes<128, 32, 4, 1>(a, st);
   if (a.Cout <= 64) return launch_planes<128, 64, 4, 2>(a, st);
   // few row tiles (13x13 layers at bs 32: 43): 128x128 tiles leave CUs idle (172 tiles for a 512-channel data
   // gradient); the 128x64 tile doubles the workgroups. YOLO_PLANES_NARROW_BELOW = tile count under which it is used
-  static const int narrow_below = [] { const char* e = getenv("YOLO_PLANES_NARROW_BELOW"); return e ? atoi(e) : 0; }();
+  static const int narrow_below = env_int("YOLO_PLANES_NARROW_BELOW", 0);
   if (((a.M + 127) / 128) * ((a.Cout + 127) / 128) < narrow_below) return launch_planes<128, 64, 4, 2>(a, st);
   // 128x128 tile: 4 waves x (64x64) for the 3x3 launches this kernel still gets (stride 2, rows longer than 64 pixels),
   // 8 waves x (32x64) for 1x1 layers -- HBM-bound, they want loads in flight (24 waves per CU instead of 12), not MFMAs
   // per barrier. YOLO_PLANES_WAVES = 2 / 4 / 8 forces one form.
-  static const int waves_env = [] { const char* e = getenv("YOLO_PLANES_WAVES"); return e ? atoi(e) : 0; }();
+  static const int waves_env = env_int("YOLO_PLANES_WAVES", 0);
   const int waves = waves_env ? waves_env : (a.ntaps == 1 && a.ncls <= 1 ? 8 : 4);
 #ifdef YOLO_PLANES_KNOCKOUTS   // diagnostic build (make KNOCKOUTS=1): compile-time knock-outs of the 128x128 4-wave kernel
   switch (a.dbg) {
@@ -684,7 +660,7 @@ int launch_gather_planes(GatherConvArgs& a, hipStream_t st) {
   if (waves == 2) return launch_planes<128, 128, 2, 1>(a, st);   // 2 waves x (64 x 128): one wave per SIMD, 512 registers
   if (waves == 4) {
     // (a.ncls > 1: the parity classes of a strided data gradient in one launch -- a.ntaps is class 0's there)
-    if (deep && a.ntaps == 1 && a.ncls <= 1) return launch_planes<128, 128, 2, 2, 128>(a, st);
+    if (deep && a.ntaps == 1 && a.ncls <= 1) return launch_planes<128, 128, 2, 2, PF_DEEP1>(a, st);
     return launch_planes<128, 128, 2, 2>(a, st);
   }
   {   // split-K (launches that leave the chip idle) lives in the 4-wave form
@@ -692,8 +668,8 @@ int launch_gather_planes(GatherConvArgs& a, hipStream_t st) {
     const int min_cb = a.ntaps >= 8 ? 1 : (8 + a.ntaps - 1) / a.ntaps;
     if (a.ncls <= 1 && conv_split_parts(a, nb, 128, min_cb, 4) > 1) return launch_planes<128, 128, 2, 2>(a, st);
   }
-  if (deep == 1 && a.ntaps == 1 && a.ncls <= 1) return launch_planes<128, 128, 4, 2, 128>(a, st);
-  if (deep == 2 && a.ntaps == 1 && a.ncls <= 1) return launch_planes<128, 128, 4, 2, 256>(a, st);
+  if (deep == 1 && a.ntaps == 1 && a.ncls <= 1) return launch_planes<128, 128, 4, 2, PF_DEEP1>(a, st);
+  if (deep == 2 && a.ntaps == 1 && a.ncls <= 1) return launch_planes<128, 128, 4, 2, PF_DEEP2>(a, st);
   return launch_planes<128, 128, 4, 2>(a, st);
 }
 

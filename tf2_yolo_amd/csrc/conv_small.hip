@@ -329,9 +329,15 @@ __global__ __launch_bounds__(64 * SM_WAVES) void conv_small_kernel(const GatherC
   }
 }
 
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
+template <int NT, int TM, int TN, int CH, bool HEAD = false>
+static bool small_limit_ok() {
+  return lds_limit_ok<conv_small_kernel<NT, TM, TN, CH, HEAD>, SmallLds<TM, TN, NT>::BYTES>("conv_small_kernel");
+}
+// Can this tile's kernel have its LDS (up to 150 KB: the 64 x 64 tile's four blocks at once)? Same table as launch_conv_small.
+static bool small_tile_fits(int ntaps, int tile, bool head) {
+  if (head) return tile != 22 ? small_limit_ok<1, 1, 1, 4, true>() : small_limit_ok<1, 2, 2, 2, true>();
+  if (ntaps == 1) return tile == 22 ? small_limit_ok<1, 2, 2, 2>() : tile == 21 ? small_limit_ok<1, 2, 1, 4>() : small_limit_ok<1, 1, 1, 4>();
+  return tile == 22 ? small_limit_ok<9, 2, 2, 2>() : tile == 21 ? small_limit_ok<9, 2, 1, 4>() : small_limit_ok<9, 1, 1, 4>();
 }
 
 // Tile of a launch, 0 = not for this kernel. Measured on YOLOv3-416 at bs 1 (profiles/r06_o_conv_small_tiles.txt, us per
@@ -350,7 +356,7 @@ static int env_int(const char* name, int dflt) {
 // training step; a 3x3 unit asks for 9x the bytes per output and is no faster than the split-K pair except at 52x52.
 // YOLO_CONV_SMALL: 0 off, 1 (default) the policy below, 3 every 3x3 unit the grid limit allows too; YOLO_CONV_SMALL_TILE = 11 / 21 / 22 forces a tile and
 // YOLO_CONV_SMALL_GRID the largest launch (experiments).
-static int small_tile(const GatherConvArgs& a) {
+static int small_tile_policy(const GatherConvArgs& a) {
   static const int on = env_int("YOLO_CONV_SMALL", 1);
   static const int tile_env = env_int("YOLO_CONV_SMALL_TILE", 0);
   static const int grid_env = env_int("YOLO_CONV_SMALL_GRID", 0);
@@ -383,26 +389,25 @@ static int small_tile(const GatherConvArgs& a) {
   return 0;
 }
 
+// (0 too when the tile's LDS limit cannot be raised: the caller then takes the kernels of the training step)
+static int small_tile(const GatherConvArgs& a) {
+  const int tile = small_tile_policy(a);
+  return tile != 0 && small_tile_fits(a.ntaps, tile, false) ? tile : 0;
+}
+
 bool conv_small_supported(const GatherConvArgs& a) { return small_tile(a) != 0; }
 
 template <int NT, int TM, int TN, int CH, bool HEAD = false>
 static int launch_small(GatherConvArgs& a, hipStream_t st, int* nwg) {
   a.nblocks = (int)(((a.M + 32 * TM - 1) / (32 * TM)) * ((a.Cout + 32 * TN - 1) / (32 * TN)));
   *nwg = a.nblocks;
-  constexpr int lds = SmallLds<TM, TN, NT>::BYTES;   // (up to 150 KB: the 64 x 64 tile's four blocks at once)
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_small_kernel<NT, TM, TN, CH, HEAD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((conv_small_kernel<NT, TM, TN, CH, HEAD>), dim3((unsigned)a.nblocks), dim3(64 * SM_WAVES), lds, st, a);
-  return check_launch("conv_small_kernel");
+  return launch_lds<conv_small_kernel<NT, TM, TN, CH, HEAD>, SmallLds<TM, TN, NT>::BYTES>(dim3((unsigned)a.nblocks), dim3(64 * SM_WAVES),
+                                                                                         st, a, "conv_small_kernel");
 }
 
 // the detection-head form: 1x1, stride 1, dense, bias, any Cout; 32 x 32 tiles while they give at most 256 workgroups, else
 // 64 x 64 while those do
-static int small_head_tile(const GatherConvArgs& a) {
+static int small_head_tile_policy(const GatherConvArgs& a) {
   static const int on = env_int("YOLO_CONV_SMALL", 1);
   if (!on || a.head_y == nullptr || a.head_anchors == nullptr || a.head_A <= 0 || a.head_C <= 0) return 0;
   if (a.ntaps != 1 || (a.Cs % 16) != 0 || a.ldw != a.Cs || a.Cout != a.head_A * (5 + a.head_C)) return 0;
@@ -413,6 +418,10 @@ static int small_head_tile(const GatherConvArgs& a) {
   if (g11 <= 256) return 11;
   if (g22 <= 256) return 22;
   return 0;
+}
+static int small_head_tile(const GatherConvArgs& a) {
+  const int tile = small_head_tile_policy(a);
+  return tile != 0 && small_tile_fits(1, tile, true) ? tile : 0;
 }
 bool conv_small_head_supported(const GatherConvArgs& a) { return small_head_tile(a) != 0; }
 

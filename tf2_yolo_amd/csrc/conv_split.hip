@@ -323,14 +323,8 @@ static int launch_split(GatherConvArgs& a, hipStream_t st) {
   }
   a.nblocks = (int)nb;
   constexpr size_t lds = 2 * 3 * (BM + BN) * SPLIT_ROW * sizeof(unsigned short);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_conv_split_kernel<BM, BN, WGM, WGN>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((gather_conv_split_kernel<BM, BN, WGM, WGN>), dim3((unsigned)nb), dim3(64 * WGM * WGN), lds, st, a);
-  return check_launch("gather_conv_split_kernel");
+  return launch_lds<gather_conv_split_kernel<BM, BN, WGM, WGN>, lds>(dim3((unsigned)nb), dim3(64 * WGM * WGN), st, a,
+                                                                     "gather_conv_split_kernel");
 }
 
 bool gather_split_supported(const GatherConvArgs& a) { return (a.Cs % SPLIT_BK) == 0 && a.Cout > 32; }
@@ -338,7 +332,7 @@ bool gather_split_supported(const GatherConvArgs& a) { return (a.Cs % SPLIT_BK) 
 int launch_gather_split(GatherConvArgs& a, hipStream_t st) {
   // 8-wave workgroups (4 waves per SIMD with two workgroups per CU) cover the per-stage barrier and the
   // split VALU better than 4-wave ones: +7 % on the 128x128 tile (YOLO_SPLIT_WAVES=4 restores 4 waves)
-  static const int waves = [] { const char* e = getenv("YOLO_SPLIT_WAVES"); return e ? atoi(e) : 8; }();
+  static const int waves = env_int("YOLO_SPLIT_WAVES", 8);
   if (a.Cout <= 64) return launch_split<128, 64, 2, 2>(a, st);
   const long long blocks128 = ((a.M + 127) / 128) * ((a.Cout + 127) / 128);
   if (blocks128 <= 512) return launch_split<64, 128, 1, 4>(a, st);   // (8 waves measured slower here)

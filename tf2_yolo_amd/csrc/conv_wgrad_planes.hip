@@ -356,25 +356,17 @@ static int launch_wp(WgradArgs& a, hipStream_t st) {
   // round; every workgroup ends with BM x BN fp32 atomics, and those run at ~1.3 TB/s chip-wide)
   // Measured: 3x3 layers are flat from 1024 to 2048 workgroups, 1x1 layers (few pixels per split, the atomics
   // of 1024 workgroups cost as much as their MFMAs) run 25 % faster at 256.
-  static const long long target_env = [] { const char* e = getenv("YOLO_WGRAD_TARGET"); return e ? atoll(e) : 0LL; }();
+  static const long long target_env = env_ll("YOLO_WGRAD_TARGET", 0LL);
   // 3x3 layers: whole rounds of the workgroups the chip holds at once (occupancy x CUs): 1026 workgroups on 768
   // slots are two rounds, the second a third full (52x52x128->256: 167 us; 756 workgroups: 154 us)
-  static int resident = 0;
-  if (resident == 0) {
-    int per_cu = 0, dev = 0, cus = 0;
-    constexpr size_t lds_q = NB * (BM / 32 + BN / 32) * PL_PLANES * 1024;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_planes_kernel<BM, BN, WGM, WGN, NB, KO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&wgrad_planes_kernel<BM, BN, WGM, WGN, NB, KO>),
-                                                     64 * WGM * WGN, lds_q) == hipSuccess &&
-        hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      resident = per_cu * cus;
-    if (resident <= 0) resident = 512;
-  }
+  constexpr size_t lds = NB * (BM / 32 + BN / 32) * PL_PLANES * 1024;
+  constexpr auto kernel = &wgrad_planes_kernel<BM, BN, WGM, WGN, NB, KO>;
+  int resident = resident_workgroups<kernel, lds>(64 * WGM * WGN, "wgrad_planes_kernel");
+  if (resident <= 0) resident = 512;
   // (round 3, slabs instead of atomics, same finding: 512 / 768 workgroups for the 1x1 layers are 12-25 % slower than 256,
   // and a deeper DMA ring (NB = 4..6) changes nothing: these launches are not bound by bytes in flight)
   // (YOLO_WGRAD_TARGET_1X1: tuning knob for the 1x1 layers)
-  static const long long target_1x1_env = [] { const char* e = getenv("YOLO_WGRAD_TARGET_1X1"); return e ? atoll(e) : 0LL; }();
+  static const long long target_1x1_env = env_ll("YOLO_WGRAD_TARGET_1X1", 0LL);
   long long target = a.ntaps == 1 ? (target_1x1_env > 0 ? target_1x1_env : 256)
                                   : (target_env > 0 ? target_env : 1024);   // (YOLO_WGRAD_TARGET: 3x3 layers only)
   if (target_env <= 0 && a.ntaps > 1) {
@@ -389,7 +381,7 @@ static int launch_wp(WgradArgs& a, hipStream_t st) {
   if (splits < 1) splits = 1;
   // reproducible form: the slabs of all workgroups must fit the registered workspace (fewer, longer splits otherwise)
   a.slabs = nullptr;
-  static const bool det_env = [] { const char* e = getenv("YOLO_WGRAD_DETERMINISTIC"); return !(e && atoi(e) == 0); }();
+  static const bool det_env = env_int("YOLO_WGRAD_DETERMINISTIC", 1) != 0;
   if (det_env && g_wgrad_ws != nullptr && g_wgrad_ws_bytes > WGRAD_WS_COLSUM_BYTES) {
     const long long cap = (long long)((g_wgrad_ws_bytes - WGRAD_WS_COLSUM_BYTES) / ((size_t)BM * BN * 4));
     if (cap >= tiles) {
@@ -407,16 +399,7 @@ static int launch_wp(WgradArgs& a, hipStream_t st) {
     return YOLO_ERR_INVALID_ARG;
   }
   a.nblocks = (int)(tiles * splits);
-  constexpr size_t lds = NB * (BM / 32 + BN / 32) * PL_PLANES * 1024;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_planes_kernel<BM, BN, WGM, WGN, NB, KO>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL((wgrad_planes_kernel<BM, BN, WGM, WGN, NB, KO>), dim3((unsigned)(tiles * splits)), dim3(64 * WGM * WGN), lds,
-                     st, a);
-  if (int rc = check_launch("wgrad_planes_kernel")) return rc;
+  if (int rc = launch_lds<kernel, lds>(dim3((unsigned)(tiles * splits)), dim3(64 * WGM * WGN), st, a, "wgrad_planes_kernel")) return rc;
   if (a.slabs != nullptr) {
     const long long pieces = tiles * (BM * BN / 4);
     hipLaunchKernelGGL((wgrad_reduce_kernel<BM, BN, WGM, WGN>), dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, a);
@@ -451,9 +434,9 @@ int launch_wgrad_planes(WgradArgs& a, hipStream_t st) {
   if (cols <= 64) return launch_wp<128, 64, 4, 2>(a, st);
   // 4 waves x (64 x 64): 12 MFMAs per wave between barriers instead of 6. Alone 160-178 us against 200-207 us on the
   // 3x3 layers; in the training step (beside the data-gradient stream) 33.25 against 33.58 ms. YOLO_WGRAD_WAVES=8: old form
-  static const int waves = [] { const char* e = getenv("YOLO_WGRAD_WAVES"); return e ? atoi(e) : 4; }();
+  static const int waves = env_int("YOLO_WGRAD_WAVES", 4);
 #ifdef YOLO_PLANES_KNOCKOUTS   // diagnostic build (make KNOCKOUTS=1)
-  static const int ko = [] { const char* e = getenv("YOLO_WGRAD_KO"); return e ? atoi(e) : 0; }();
+  static const int ko = env_int("YOLO_WGRAD_KO", 0);
   switch (ko) {
     case 1: return launch_wp<128, 128, 2, 2, 3, 1>(a, st);
     case 2: return launch_wp<128, 128, 2, 2, 3, 2>(a, st);
@@ -469,7 +452,7 @@ int launch_wgrad_planes(WgradArgs& a, hipStream_t st) {
   // busy as the matrix cores. Measured alone: 13x13x512->1024 188 -> 160 us, 26x26 +-0, 52x52 / 104x104 5-10 % slower (two
   // workgroups per CU instead of three), 1x1 layers 30 % slower: used for the 3x3 layers with few pixels (YOLO_WGRAD_WIDE:
   // 0 never, 1 wherever the shape allows, 2 = that policy)
-  static const int wide = [] { const char* e = getenv("YOLO_WGRAD_WIDE"); return e ? atoi(e) : 2; }();
+  static const int wide = env_int("YOLO_WGRAD_WIDE", 2);
   if (cols >= 256 && (wide == 1 || (wide == 2 && a.ntaps > 1 && a.M <= 8192))) return launch_wp<128, 256, 2, 2>(a, st);
   if (waves == 4) return launch_wp<128, 128, 2, 2>(a, st);
   return launch_wp<128, 128, 4, 2>(a, st);

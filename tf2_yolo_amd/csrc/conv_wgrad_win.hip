@@ -853,31 +853,33 @@ bool wgrad_win_supported(const WgradArgs& a) {
   return true;
 }
 
+// The kernels address their dynamic LDS from 0 (immediate offsets in the window reads): true only while no static __shared__
+// sits in front of it. Checked on the host, once per kernel, instead of trapping on the device.
+template <auto Kernel>
+static bool lds_starts_at_zero() {
+  static const bool ok = [] {
+    hipFuncAttributes fa{};
+    return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(Kernel)) == hipSuccess && fa.sharedSizeBytes == 0;
+  }();
+  return ok;
+}
+
+// the one-ring kernel of a launch_ww<RING, KO, PF, M16>: the 16x16x32-MFMA form (M16) has no PF
+template <int RING, int KO, int PF, bool M16>
+constexpr auto ww_kernel = M16 ? &wgrad_win16_kernel<RING, KO> : &wgrad_win_kernel<RING, KO, PF>;
+
+// Returns 1 = "not covered" (the LDS layout assumption does not hold, or the LDS limit cannot be raised): the caller then runs
+// the per-tap kernel.
 template <int RING, int KO, int PF = 1, bool M16 = false>
 static int launch_ww(WgradArgs& a, hipStream_t st) {
-  const void* kfn = M16 ? reinterpret_cast<const void*>(&wgrad_win16_kernel<RING, KO>)
-                        : reinterpret_cast<const void*>(&wgrad_win_kernel<RING, KO, PF>);
+  constexpr auto kernel = ww_kernel<RING, KO, PF, M16>;
   a.tiles_co = a.Cout / WW_CO;
   a.tiles_j = a.Cs / WW_CI;
   const long long tiles = (long long)a.tiles_co * a.tiles_j;
   constexpr size_t lds = 2 * (2 * 4 * PL_PLANES * 1024) + 2 * (RING * 64 + 64);
-  static int resident = 0;
-  static bool lds_from_zero = true;
-  if (resident == 0) {
-    int per_cu = 0, dev = 0, cus = 0;
-    // the kernels address their dynamic LDS from 0 (immediate offsets in the window reads): true only while no static
-    // __shared__ sits in front of it. Checked here instead of trapping on the device; 1 = "not covered", the caller then
-    // runs the per-tap kernel.
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, kfn) != hipSuccess || fa.sharedSizeBytes != 0) lds_from_zero = false;
-    (void)hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 256, lds) ==
-            hipSuccess &&
-        hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      resident = per_cu * cus;
-    if (resident <= 0) resident = 512;
-  }
-  if (!lds_from_zero) return 1;
+  if (!lds_starts_at_zero<kernel>() || !lds_limit_ok<kernel, lds>("wgrad_win_kernel")) return 1;
+  int resident = resident_workgroups<kernel, lds>(256, "wgrad_win_kernel");
+  if (resident <= 0) resident = 512;
   // ONE workgroup per CU -- half of what the chip holds at once (256 on 256 CUs; round 6), at least 8 stages per workgroup.
   // Until round 5 the target was a full round of resident workgroups (two per CU). Alone the kernel prefers that; in the step
   // it is a LEAF on a stream with slack, and every workgroup it keeps resident takes 65 KB of a CU's LDS from the compute
@@ -889,14 +891,14 @@ static int launch_ww(WgradArgs& a, hipStream_t st) {
   // 256, and below 256 this kernel -- throttled on purpose -- becomes the one with the most device time in the step, so that
   // the step's roofline line would describe a launch that is not trying to fill the chip. YOLO_WGRAD_WIN_TARGET=128 is the
   // better setting for YOLOv4-608 (compute stream 98 % busy, filter-gradient stream with 20 % slack).
-  static const long long target_env = [] { const char* e = getenv("YOLO_WGRAD_WIN_TARGET"); return e ? atoll(e) : 0LL; }();
+  static const long long target_env = env_ll("YOLO_WGRAD_WIN_TARGET", 0LL);
   const long long target = target_env > 0 ? target_env : (resident >= 2 ? resident / 2 : resident);
   long long splits = target / tiles;
   const long long max_splits = (a.M + 255) / 256;
   if (splits > max_splits) splits = max_splits;
   if (splits < 1) splits = 1;
   a.slabs = nullptr;
-  static const bool det_env = [] { const char* e = getenv("YOLO_WGRAD_DETERMINISTIC"); return !(e && atoi(e) == 0); }();
+  static const bool det_env = env_int("YOLO_WGRAD_DETERMINISTIC", 1) != 0;
   size_t ws_bytes = 0;
   void* ws = wgrad_workspace(&ws_bytes);
   if (det_env && ws != nullptr && ws_bytes > WGRAD_WS_COLSUM_BYTES) {
@@ -915,9 +917,7 @@ static int launch_ww(WgradArgs& a, hipStream_t st) {
   // (one split -- the small layers of a small batch -- still goes through its slab: measured round 6, a tile's owner adding
   // to dw itself with scalar read-modify-writes costs the kernel what the slab + reduce launch cost: 44 vs 25 + 17 us, and
   // the 128 x 256 per-tap tile 103 vs 22 + 27 us)
-  if constexpr (M16) hipLaunchKernelGGL((wgrad_win16_kernel<RING, KO>), dim3((unsigned)a.nblocks), dim3(256), lds, st, a);
-  else hipLaunchKernelGGL((wgrad_win_kernel<RING, KO, PF>), dim3((unsigned)a.nblocks), dim3(256), lds, st, a);
-  if (int rc = check_launch("wgrad_win_kernel")) return rc;
+  if (int rc = launch_lds<kernel, lds>(dim3((unsigned)a.nblocks), dim3(256), st, a, "wgrad_win_kernel")) return rc;
   if (a.slabs != nullptr) {
     const long long pieces = tiles * (WW_TILE_FLOATS / 4);
     if constexpr (M16) hipLaunchKernelGGL(wgrad_win16_reduce_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, a);
@@ -930,31 +930,19 @@ static int launch_ww(WgradArgs& a, hipStream_t st) {
 // the two-half kernel (RING = 256 only: two rings of 512 slots do not fit a CU's LDS)
 static int launch_ww2(WgradArgs& a, hipStream_t st) {
   constexpr int RING = 256;
-  const void* kfn = reinterpret_cast<const void*>(&wgrad_win2_kernel<RING>);
+  constexpr auto kernel = &wgrad_win2_kernel<RING>;
   a.tiles_co = a.Cout / WW_CO;
   a.tiles_j = a.Cs / WW_CI;
   const long long tiles = (long long)a.tiles_co * a.tiles_j;
   constexpr size_t half_bytes = 2 * (2 * 4 * PL_PLANES * 1024) + 2 * (RING * 64 + 64);
   constexpr size_t handover = (size_t)WW_TILE_FLOATS * 4;
   constexpr size_t lds = 2 * half_bytes > handover ? 2 * half_bytes : handover;
-  static int resident = 0;
-  static bool ok = true;
-  if (resident == 0) {
-    int per_cu = 0, dev = 0, cus = 0;
-    hipFuncAttributes fa{};
-    if (hipFuncGetAttributes(&fa, kfn) != hipSuccess || fa.sharedSizeBytes != 0) ok = false;   // (dynamic LDS must start at 0)
-    if (hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) ok = false;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kfn, 512, lds) == hipSuccess && per_cu >= 1 &&
-        hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      resident = per_cu * cus;
-    else
-      ok = false;
-    if (resident <= 0) resident = 256;
-  }
-  if (!ok) return 1;
+  if (!lds_starts_at_zero<kernel>()) return 1;
+  const int resident = resident_workgroups<kernel, lds>(512, "wgrad_win2_kernel");
+  if (resident <= 0) return 1;   // (the limit cannot be raised, the kernel does not fit a CU, or a query failed)
   size_t ws_bytes = 0;
   void* ws = wgrad_workspace(&ws_bytes);
-  static const bool det_env = [] { const char* e = getenv("YOLO_WGRAD_DETERMINISTIC"); return !(e && atoi(e) == 0); }();
+  static const bool det_env = env_int("YOLO_WGRAD_DETERMINISTIC", 1) != 0;
   if (!det_env || ws == nullptr || ws_bytes <= WGRAD_WS_COLSUM_BYTES) return 1;   // (the atomics fallback stays with the 4-wave kernel)
   long long splits = resident / tiles;
   const long long max_splits = (a.M + 511) / 512;   // at least 8 stages per half
@@ -970,8 +958,7 @@ static int launch_ww2(WgradArgs& a, hipStream_t st) {
   a.chunk = chunk;
   a.splits = (int)splits;
   a.nblocks = (int)(tiles * splits);
-  hipLaunchKernelGGL((wgrad_win2_kernel<RING>), dim3((unsigned)a.nblocks), dim3(512), lds, st, a);
-  if (int rc = check_launch("wgrad_win2_kernel")) return rc;
+  if (int rc = launch_lds<kernel, lds>(dim3((unsigned)a.nblocks), dim3(512), st, a, "wgrad_win2_kernel")) return rc;
   const long long pieces = tiles * (WW_TILE_FLOATS / 4);
   hipLaunchKernelGGL(wgrad_win_reduce_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, a);
   return check_launch("wgrad_win_reduce_kernel");
@@ -984,7 +971,7 @@ int launch_wgrad_win(WgradArgs& a, hipStream_t st) {
     if (rc != 1) return rc;
   }
 #ifdef YOLO_PLANES_KNOCKOUTS   // diagnostic build (make KNOCKOUTS=1)
-  static const int ko = [] { const char* e = getenv("YOLO_WGRAD_KO"); return e ? atoi(e) : 0; }();
+  static const int ko = env_int("YOLO_WGRAD_KO", 0);
   if (small) switch (ko) {
       case 1: return launch_ww<256, 1>(a, st);
       case 2: return launch_ww<256, 2>(a, st);

@@ -754,6 +754,15 @@ int launch_split_reduce(GatherConvArgs& a, int bm, hipStream_t st) {
 
 float* conv_split_slabs() { return reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(g_sk_ws) + SK_TICKETS * 4); }
 
+// The forms of conv_win_kernel<WGM, NCH, STAMPS, SPLIT, SK, WGN, GEO, BNRED> that are launched, each named once
+template <int WGM, int NCH> constexpr auto win_plain = &conv_win_kernel<WGM, NCH>;
+template <int WGM, int NCH> constexpr auto win_stamped = &conv_win_kernel<WGM, NCH, true>;                       // diagnostics
+template <int WGM, int NCH> constexpr auto win_split = &conv_win_kernel<WGM, NCH, false, true>;                  // split-K
+template <int WGM, int NCH> constexpr auto win_streamk = &conv_win_kernel<WGM, NCH, false, false, true>;
+template <int WGM, int NCH> constexpr auto win_bnred = &conv_win_kernel<WGM, NCH, false, false, false, 2, 0, true>;   // fused BatchNorm-backward reduction
+template <int WGM, int NCH, int WGN> constexpr auto win_patch = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1>;
+template <int WGM, int NCH, int WGN> constexpr auto win_patch_bnred = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1, true>;
+
 template <int WGM, int NCH>
 static int launch_win(GatherConvArgs& a, hipStream_t st) {
   constexpr int BM = 64 * WGM;
@@ -768,19 +777,9 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
   a.bwd_nslots = (int)tiles_m;
   YOLO_BNRED_CHECK(a)
   constexpr size_t lds = 2 * NCH * 4096 + 3 * 8192;
-  static bool attr_set = false;
-  static int resident = 0;   // workgroups the chip holds at once (occupancy x CUs)
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<WGM, NCH>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-    int per_cu = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&conv_win_kernel<WGM, NCH>),
-                                                     128 * WGM, lds) == hipSuccess &&
-        hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      resident = per_cu * cus;
-  }
+  const dim3 block(128 * WGM);
+  // workgroups the chip holds at once (occupancy x CUs); 0 (a query failed): no stream-K
+  const int resident = resident_workgroups<win_plain<WGM, NCH>, lds>(128 * WGM, "conv_win_kernel");
   // filters of 8 MB and more (the 13x13 3x3 layers): row tile fastest. Measured on the 13x13x1024->512 data gradient
   // (172 tiles, each streaming 4.7 MB of filters): 977 MB beyond-L2 per launch = 6 TB/s with the column tile fastest.
   {
@@ -801,33 +800,19 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
   // blocks (26x26: 41 us, 52x52: 24 us) do not gain at any split)
   // YOLO_CONV_SK=1 (default): split-K with the reduce kernel (conv_split_parts); -1: the stream-K policy above
   if (a.bwd_y != nullptr) {   // the fused BatchNorm-backward reduction: one workgroup per tile, its own instantiation
-    static bool attr_bn = false;
-    if (!attr_bn) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<WGM, NCH, false, false, false, 2, 0, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_bn = true;
-    }
     a.split_parts = 1;
-    hipLaunchKernelGGL((conv_win_kernel<WGM, NCH, false, false, false, 2, 0, true>), dim3(grid), dim3(128 * WGM), lds, st, a);
-    return check_launch("conv_win_kernel(bn reduce)");
+    return launch_lds<win_bnred<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(bn reduce)");
   }
   // (parts of at least 2 channel blocks = 18 stages; YOLO_WIN_SPLIT_MIN_CB = 1: twice the parts, half the stages)
-  static const int split_min_cb = [] { const char* e = getenv("YOLO_WIN_SPLIT_MIN_CB"); return e ? atoi(e) : 2; }();
+  static const int split_min_cb = env_int("YOLO_WIN_SPLIT_MIN_CB", 2);
   a.split_parts = WGM == 2 ? conv_split_parts(a, nb, BM, split_min_cb, 2) : 1;
   if (a.split_parts > 1) {
     a.tile_order = 0;
     a.sk_grid = (int)(nb * a.split_parts);
     a.sk_slabs = conv_split_slabs();
-    if constexpr (WGM == 2) {
-      static bool attr_split = false;
-      if (!attr_split) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<WGM, NCH, false, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr_split = true;
-      }
-      hipLaunchKernelGGL((conv_win_kernel<WGM, NCH, false, true>), dim3((unsigned)a.sk_grid), dim3(128 * WGM), lds, st, a);
+    if constexpr (WGM == 2) {   // (conv_split_parts is asked for the 128-row tile only)
+      if (int rc = launch_lds<win_split<WGM, NCH>, lds>(dim3((unsigned)a.sk_grid), block, st, a, "conv_win_kernel(split)")) return rc;
     }
-    if (int rc = check_launch("conv_win_kernel(split)")) return rc;
     return launch_split_reduce(a, BM, st);
   }
   const bool sk_auto = g_opt[OPT_CONV_SK] == -1 && nb * 2 < resident && (a.Cs >> 4) >= 32;
@@ -845,29 +830,12 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
   }
   if constexpr (WGM == 2 && NCH == 5) {   // the one stamped instantiation (diagnostics on the 52x52 layers)
     if (g_opt[OPT_STAMPS] != 0 && g_dbg_buf != nullptr && g_dbg_bytes >= (size_t)nb * 128) {
-      static bool attr2 = false;
-      if (!attr2) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<WGM, NCH, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        attr2 = true;
-      }
       a.stamps = reinterpret_cast<unsigned long long*>(g_dbg_buf);
-      hipLaunchKernelGGL((conv_win_kernel<WGM, NCH, true>), dim3(grid), dim3(128 * WGM), lds, st, a);
-      return check_launch("conv_win_kernel(stamps)");
+      return launch_lds<win_stamped<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(stamps)");
     }
   }
-  if (a.sk_grid > 0) {
-    static bool attr_sk = false;
-    if (!attr_sk) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_win_kernel<WGM, NCH, false, false, true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_sk = true;
-    }
-    hipLaunchKernelGGL((conv_win_kernel<WGM, NCH, false, false, true>), dim3(grid), dim3(128 * WGM), lds, st, a);
-    return check_launch("conv_win_kernel(stream-K)");
-  }
-  hipLaunchKernelGGL((conv_win_kernel<WGM, NCH>), dim3(grid), dim3(128 * WGM), lds, st, a);
-  return check_launch("conv_win_kernel");
+  if (a.sk_grid > 0) return launch_lds<win_streamk<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(stream-K)");
+  return launch_lds<win_plain<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel");
 }
 
 // ---- patch geometry (GEO = 1): rows longer than 64 pixels, and 64-column tiles for Cout <= 64 ----
@@ -895,28 +863,13 @@ static int launch_patch(GatherConvArgs& a, hipStream_t st) {
   a.bwd_nslots = (int)tiles_m;
   YOLO_BNRED_CHECK(a)
   constexpr size_t lds = 2 * NCH * 4096 + 3 * 4096 * WGN;
-  auto kern = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
   a.tile_order = 0;   // column tile fastest: the column tiles of a patch share its window in L2
   a.sk_grid = 0;
   a.split_parts = 1;
   a.dbg = g_opt[OPT_DBG];
-  if (a.bwd_y != nullptr) {
-    auto kern_bn = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1, true>;
-    static bool attr_bn = false;
-    if (!attr_bn) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern_bn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_bn = true;
-    }
-    hipLaunchKernelGGL(kern_bn, dim3((unsigned)nb), dim3(64 * WGM * WGN), lds, st, a);
-    return check_launch("conv_win_kernel(patch, bn reduce)");
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)nb), dim3(64 * WGM * WGN), lds, st, a);
-  return check_launch("conv_win_kernel(patch)");
+  const dim3 grid((unsigned)nb), block(64 * WGM * WGN);
+  if (a.bwd_y == nullptr) return launch_lds<win_patch<WGM, NCH, WGN>, lds>(grid, block, st, a, "conv_win_kernel(patch)");
+  return launch_lds<win_patch_bnred<WGM, NCH, WGN>, lds>(grid, block, st, a, "conv_win_kernel(patch, bn reduce)");
 }
 
 // Policy of the patch form (YOLO_CONV_PATCH / yolo_set_option key 5): 0 = off, 1 = automatic (rows longer than 64

@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void maxpool_plane_bwd_kernel(const float* __r
 }
 
 static bool pool_plane_ok(int H, int W, int C, int k, int s, int Ho, int Wo) {
-  static const bool on = [] { const char* e = getenv("YOLO_POOL_PLANE"); return !(e && atoi(e) == 0); }();
+  static const bool on = env_int("YOLO_POOL_PLANE", 1) != 0;
   return on && s == 1 && Ho == H && Wo == W && k >= 4 && (C % POOL_CG) == 0 && H * W <= 1024;
 }
 

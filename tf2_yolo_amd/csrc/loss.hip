@@ -620,7 +620,7 @@ extern "C" int yolo_loss_fwd_bwd(const yolo_loss_cfg* cfg, const float* y_true, 
   dim3 grid((unsigned)blocks), block(256);
   // the loader that requests a whole cell one cell ahead (loss_kernel<VER, true>): v2 / v3 / v4, at most 256 prediction
   // channels per cell; YOLO_LOSS_PREFETCH=0 keeps the chunk-ahead loader (A/B, tests: the two must agree bit for bit)
-  static const bool pref_env = [] { const char* e = getenv("YOLO_LOSS_PREFETCH"); return !(e && atoi(e) == 0); }();
+  static const bool pref_env = env_int("YOLO_LOSS_PREFETCH", 1) != 0;
   const bool pref = pref_env && !(g_opt[OPT_EXP] & 8) && cfg->version != 1 && cfg->A * (5 + cfg->C) <= 256;
   switch (cfg->version) {
     case 1: hipLaunchKernelGGL((loss_kernel<1, false>), grid, block, 0, st, lp, y_true, y_pred, dpred, loss_out); break;

@@ -21,26 +21,20 @@ void* g_dbg_buf = nullptr;
 size_t g_dbg_bytes = 0;
 static void options_from_env() {
   for (int i = 0; i < OPT_COUNT; ++i) g_opt[i] = 0;
-  const char* e = getenv("YOLO_CONV_WIN");       // 0 off, 1 automatic, 2 force 128x128 tiles, 4 force 256x128 tiles
-  g_opt[OPT_CONV_WIN] = e ? atoi(e) : 1;
+  g_opt[OPT_CONV_WIN] = env_int("YOLO_CONV_WIN", 1);   // 0 off, 1 automatic, 2 force 128x128 tiles, 4 force 256x128 tiles
   // launches that would leave most of the chip idle (needs yolo_set_conv_workspace): 0 = one workgroup per tile,
   // 1 = split-K with a reduce kernel (window and per-tap kernels), -1 = stream-K form of the window kernel (tile
   // tickets, the last arriver combines), > 1 = stream-K with that many workgroups (benchmarks, tests)
-  e = getenv("YOLO_CONV_SK");
-  g_opt[OPT_CONV_SK] = e ? atoi(e) : 1;
+  g_opt[OPT_CONV_SK] = env_int("YOLO_CONV_SK", 1);
   // 3x3 stride-1 window kernel on 2-D patches (conv_win.hip, GEO = 1): 0 off, 1 automatic, 2 wherever the shape allows
-  e = getenv("YOLO_CONV_PATCH");
-  g_opt[OPT_CONV_PATCH] = e ? atoi(e) : 1;
+  g_opt[OPT_CONV_PATCH] = env_int("YOLO_CONV_PATCH", 1);
   // 3x3 stride-1 filter gradient with the input window in LDS (conv_wgrad_win.hip): 0 off, wherever the shape allows: 1 = on
   // v_mfma_f32_32x32x16_f16, 2 = that with fragment reads two tap-steps ahead, 3 = on v_mfma_f32_16x16x32_f16 (default 1: 3 is 4 % faster alone, equal in the step)
-  e = getenv("YOLO_WGRAD_WIN");
-  g_opt[OPT_WGRAD_WIN] = e ? atoi(e) : 1;
+  g_opt[OPT_WGRAD_WIN] = env_int("YOLO_WGRAD_WIN", 1);
   // hard / DIoU NMS: 0 = pair tests as a bit matrix by the whole chip + per-class walk over the bits (classes of up to 8192
   // rows; larger ones walk), 1 = the greedy walk kernel for every class (tests: both must give the same rows)
-  e = getenv("YOLO_NMS_WALK");
-  g_opt[OPT_NMS_WALK] = e ? atoi(e) : 0;
-  e = getenv("YOLO_EXP");   // experiment / A-B bits (conv_args.hpp: OPT_EXP)
-  g_opt[OPT_EXP] = e ? atoi(e) : 0;
+  g_opt[OPT_NMS_WALK] = env_int("YOLO_NMS_WALK", 0);
+  g_opt[OPT_EXP] = env_int("YOLO_EXP", 0);   // experiment / A-B bits (conv_args.hpp: OPT_EXP)
 }
 void init_options() {
   static bool done = false;

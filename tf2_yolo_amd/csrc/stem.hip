@@ -459,12 +459,12 @@ __global__ __launch_bounds__(256) void stem_mfma_kernel(const float* __restrict_
 static int stem_mfma_per_cu() {
   // the fp32 matrix-core form (stem_mfma_kernel) is the default: 8 workgroups per CU; YOLO_STEM_MFMA=0 selects the FMA kernel
   // (same-box A/B of the whole step: 29.98 -> 29.87 ms)
-  static const int v = [] { const char* e = getenv("YOLO_STEM_MFMA"); return e ? atoi(e) : 8; }();
+  static const int v = env_int("YOLO_STEM_MFMA", 8);
   return v;
 }
 
 bool stem_fwd_supported(const yolo_conv_desc* d) {
-  static const bool on = [] { const char* e = getenv("YOLO_STEM_DIRECT"); return !(e && atoi(e) == 0); }();
+  static const bool on = env_int("YOLO_STEM_DIRECT", 1) != 0;
   // (the FMA kernel below ~1 M pixels - bs 1 inference - gives a lane a single pixel and is bound by the latency of its
   // filter loads: the implicit-GEMM kernel is faster there; the matrix-core form has no such floor)
   const long long M = (long long)d->N * d->H * d->W;
@@ -478,7 +478,7 @@ int launch_stem_fwd(const yolo_conv_desc* d, const float* x, const float* w, con
   const bool st_on = stats != nullptr || absmax != nullptr;
   // one resident round: every lane walks M / (grid * 256) pixels (a second, partial round would idle most CUs)
   // YOLO_STEM_SREG=0: the filter broadcast from LDS (round 1's kernel) instead of the scalar cache
-  static const bool sreg = [] { const char* e = getenv("YOLO_STEM_SREG"); return !(e && atoi(e) == 0); }();
+  static const bool sreg = env_int("YOLO_STEM_SREG", 1) != 0;
   static float* wt_ring = nullptr;   // 8 prepared filters (3.5 KB each), used round robin: launches in flight never share one
   static unsigned wt_next = 0;        // (a __device__ array of the library: nothing is allocated at run time)
   if (sreg && wt_ring == nullptr &&
