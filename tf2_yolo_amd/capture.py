@@ -22,6 +22,18 @@ step mode) keeps the two streams. The optimizer's step-dependent scalars (the
 bias-corrected rate, 1/world) live in device memory and are refreshed before each replay (Adam.refresh_hyper), so the
 captured launches never change. Results are bit-identical to the eager step (same kernels, same order, same operands;
 the filter-gradient reductions are atomics-free: ops.ensure_wgrad_workspace).
+
+What a recording may assume about the network. A recording holds only the calls the recorded step made, and it is replayed
+for as long as its key holds, whatever runs between two replays. So it may rely on what the key names -- batch shape and
+allocation (Network.alloc_gen: every buffer address), losses, optimizer, reducer, trainable anchors -- and on the two
+eager steps in front of it (buffers allocated, job tables built, lazy initialisation done), and on NOTHING the host caches
+about the device: the validity flags of the filter planes, of the transposed filters and of their planes (Network._wp_valid,
+_wT_valid, _wTp_valid) belong to whatever ran last -- an inference pass, a training-mode forward without backward --
+and a step recorded while one of them is set would lack that refresh in every replay: Adam would go on updating `params`
+while the convolutions read the planes of the weights of the recorded step. Both recorders therefore start from
+Network.mark_params_changed() (pending events of the second stream waited for, every flag cleared, inference graphs
+dropped): the recorded step is the FULL step, the one that follows an optimizer update, which is what every replay follows.
+Once per recording; a replay costs what it did.
 """
 import torch
 
@@ -50,7 +62,8 @@ class _StaticInputs:
 
 
 class StepGraphs:
-    """Captured training step of one Model for one (batch size, loss list, optimizer, reducer) configuration."""
+    """Captured training step of one Model for one (batch size, loss list, optimizer, reducer) configuration. The capture
+    starts from Network.mark_params_changed(), so it holds the full step whatever ran before it (module docstring)."""
 
     def __init__(self, model, x, y_list):
         self.model = model
@@ -64,6 +77,7 @@ class StepGraphs:
         self.x, self.ys = self.inputs.x, self.inputs.ys
         self.segments = []          # (graph, action): action = ("reduce", bucket) | ("finish",) | None
         opt._hyper_buffers()        # (pinned host + device scalars: allocated here, never inside a capture)
+        net.mark_params_changed()   # record the full step, whatever ran last (module docstring)
         torch.cuda.synchronize()
         self._capture(net, opt)
 
@@ -170,7 +184,8 @@ class StepGraphs:
 
 class StepTape:
     """The recorded training step of one Model (tape.py): same key, same replay interface as StepGraphs. Recording
-    EXECUTES the step (it is an ordinary eager step whose library calls are remembered), so `record` returns its losses."""
+    EXECUTES the step (it is an ordinary eager step whose library calls are remembered), so `record` returns its losses.
+    Like StepGraphs it records from Network.mark_params_changed(): no host-side validity flag shortens the tape."""
 
     def __init__(self, model, x, y_list):
         from . import tape as tape_mod
@@ -186,6 +201,7 @@ class StepTape:
         # (events of the eager steps before: the recorded step must not wait for objects no replay will ever re-record;
         # the two streams were joined at the end of the last backward)
         net._dyp_events = [None, None]
+        net.mark_params_changed()   # record the full step, whatever ran last (module docstring)
         self.tape = tape_mod.Tape()
         opt.refresh_hyper(grad_scale=(1.0 / red.world) if red is not None else 1.0)
         tape_mod.ACTIVE = self.tape
