@@ -564,6 +564,44 @@ int yolo_sgd_step(float* p, float* g, long long n, float lr, float grad_scale, i
 int yolo_fill(float* p, long long n, float value, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Gradient norms, clipping, and the optimizer forms built on them (csrc/optim.hip).
+ *
+ * The flat buffers are walked through a CHUNK TABLE in device memory, built once by the host: chunk c covers elements
+ * [chunk_off[c], chunk_off[c] + chunk_len[c]) of variable chunk_var[c]. A chunk never straddles two variables and never
+ * covers the padding between them; the chunks of variable v are the consecutive indices [var_first[v], var_first[v+1])
+ * (var_first has n_vars + 1 entries). One workgroup runs per chunk.
+ *
+ * hyper: device float[8], refreshed by the host before every step, so that a recorded step replays unchanged:
+ *   [0] lr (Adam: yolo_adam_lr_t of the step)  [1] beta1  [2] beta2  [3] eps  [4] grad_scale  [5] momentum
+ *   [6] clip threshold  [7] unused
+ * clip_mode: 0 none, 1 per-variable norm (tf.clip_by_norm), 2 global norm (tf.clip_by_global_norm), 3 value.
+ * None of these calls allocates, copies to the host or synchronises.
+ * ------------------------------------------------------------------------------------ */
+/* Squared L2 norms in double: var_sq[v] per variable, *total_sq = their sum in variable order. Stage 1 writes one partial
+ * per chunk into the workspace, stage 2 adds the partials of each variable in index order: no atomics, one value whatever
+ * the timing. */
+size_t yolo_grad_sqnorm_workspace_bytes(int n_chunks);
+int yolo_grad_sqnorm(const float* g, const long long* chunk_off, const int* chunk_len, int n_chunks,
+                     const int* var_first, int n_vars, double* var_sq, double* total_sq, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* factors[v] = t / max(|gs| * sqrt(var_sq[v]), t) (mode 1, n_vars factors) or factors[0] = t / max(global norm, t) (mode 2),
+ * in double, rounded once to float: exactly 1 at or below the threshold t = hyper[6]. The global norm is
+ * |gs| * sqrt(*total_sq + *total_sq_extra) (total_sq_extra may be NULL: the trainable anchors' sum, added second);
+ * it is also written to *norm_out as a float unless norm_out is NULL. */
+int yolo_clip_factors(const double* var_sq, int n_vars, const double* total_sq, const double* total_sq_extra,
+                      const float* hyper, int mode, float* factors, float* norm_out, void* stream);
+/* gg = (g * gs) * c, or clamp(g * gs, -t, +t) in mode 3; then the m / v / p arithmetic of yolo_adam_step. With vhat != NULL
+ * (AMSGrad): vhat = max(vhat, v), p -= lr_t * m / (sqrt(vhat) + eps). factors may be NULL in modes 0 and 3. */
+int yolo_adam_step_clip(float* p, float* g, float* m, float* v, float* vhat, const long long* chunk_off,
+                        const int* chunk_len, const int* chunk_var, int n_chunks, const float* hyper,
+                        const float* factors, int clip_mode, int zero_grad, void* stream);
+/* Keras momentum SGD on the same gg: accum = mu * accum - lr * gg; p += accum, or with nesterov p += mu * accum - lr * gg.
+ * accum == NULL: no momentum, p -= lr * gg. */
+int yolo_sgd_step_clip(float* p, float* g, float* accum, int nesterov, const long long* chunk_off,
+                       const int* chunk_len, const int* chunk_var, int n_chunks, const float* hyper,
+                       const float* factors, int clip_mode, int zero_grad, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * decode + NMS (utils/tools.py:370-438, 630-786), bit-exact index selection.
  * ------------------------------------------------------------------------------------ */
 /* One level: pred [gh,gw,A*(5+C)] float32 (version 2/3/4) or [gh,gw,5B+C] (version 1).

@@ -131,6 +131,11 @@ SIGNATURES = {
     "yolo_adam_step_dev": (c_int, [_P, _P, _P, _P, _LL, _P, c_int, _P]),
     "yolo_sgd_step": (c_int, [_P, _P, _LL, c_float, c_float, c_int, _P]),
     "yolo_fill": (c_int, [_P, _LL, c_float, _P]),
+    "yolo_grad_sqnorm_workspace_bytes": (c_size_t, [c_int]),
+    "yolo_grad_sqnorm": (c_int, [_P, _P, _P, c_int, _P, c_int, _P, _P, _P, c_size_t, _P]),
+    "yolo_clip_factors": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, _P, _P]),
+    "yolo_adam_step_clip": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int, _P, _P, c_int, c_int, _P]),
+    "yolo_sgd_step_clip": (c_int, [_P, _P, _P, c_int, _P, _P, _P, c_int, _P, _P, c_int, c_int, _P]),
     "yolo_decode_level": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_float, _P, c_int, _P, _P, c_size_t, _P]),
     "yolo_decode_level_f64": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_double, _P, c_int, _P, _P,
                                       c_size_t, _P]),
@@ -152,6 +157,7 @@ _lib = None
 _QUERIES = {"yolo_last_error", "yolo_abi_version", "yolo_bnred_slots_cap", "yolo_device_available", "yolo_conv_workspace_bytes", "yolo_planes_bytes",
             "yolo_stem_bwd_scratch_bytes", "yolo_loss_workspace_bytes", "yolo_decode_workspace_bytes",
             "yolo_nms_workspace_bytes", "yolo_pr_curve_workspace_bytes", "yolo_wgrad_workspace_bytes", "yolo_adam_lr_t",
+            "yolo_grad_sqnorm_workspace_bytes",
             "yolo_set_option", "yolo_set_debug_buffer", "yolo_set_conv_workspace", "yolo_set_wgrad_workspace"}
 
 

@@ -1158,6 +1158,117 @@ def sgd_step(p, g, lr, grad_scale=1.0, zero_grad=True):
           "yolo_sgd_step")
 
 
+# ---- gradient norms, clipping, and the optimizer forms built on them (csrc/optim.hip) ----
+OPT_CHUNK = 8192            # floats per chunk = the work of one workgroup
+CLIP_NONE, CLIP_NORM, CLIP_GLOBAL, CLIP_VALUE = 0, 1, 2, 3
+OPT_HYPER = 8               # floats of the device scalars: lr, beta1, beta2, eps, grad_scale, momentum, clip threshold, -
+
+
+def build_chunk_table(variables, chunk=OPT_CHUNK):
+    """Pure host function. variables: (offset, size) pairs of a flat buffer, in order, not overlapping. Returns numpy arrays
+    chunk_off int64[C], chunk_len int32[C], chunk_var int32[C], var_first int32[V + 1]: every element of every variable is
+    in exactly one chunk, a chunk lies inside one variable (so no padding is in any chunk), and variable v owns the
+    consecutive chunks var_first[v] .. var_first[v + 1] - 1, in address order."""
+    import numpy as np
+    if chunk <= 0 or chunk % 4:
+        raise ValueError("chunk must be a positive multiple of 4 floats")
+    offs, lens, owner, first = [], [], [], [0]
+    end = 0
+    for v, (off, size) in enumerate(variables):
+        off, size = int(off), int(size)
+        if off < end or size < 0:
+            raise ValueError(f"variable {v} (offset {off}, size {size}) overlaps the one before it")
+        end = off + size
+        for o in range(off, end, chunk):
+            offs.append(o)
+            lens.append(min(chunk, end - o))
+            owner.append(v)
+        first.append(len(offs))
+    return (np.asarray(offs, dtype=np.int64), np.asarray(lens, dtype=np.int32), np.asarray(owner, dtype=np.int32),
+            np.asarray(first, dtype=np.int32))
+
+
+class ChunkTable:
+    """build_chunk_table in device memory, with the buffers the norm calls need: var_sq double[V], total_sq double[1] and
+    the stage-1 workspace (allocated here, once: the calls themselves allocate nothing)"""
+
+    def __init__(self, variables, chunk=OPT_CHUNK, device="cuda"):
+        off, ln, var, first = build_chunk_table(variables, chunk)
+        if len(off) == 0:
+            raise YoloHipError("ChunkTable: no elements")
+        self.n_chunks, self.n_vars = len(off), len(first) - 1
+        self.extent = int(off[-1] + ln[-1])          # one past the last element any chunk touches
+        self.off, self.len, self.var, self.first = (torch.from_numpy(a).to(device) for a in (off, ln, var, first))
+        self.var_sq = torch.zeros(self.n_vars, dtype=torch.float64, device=device)
+        self.total_sq = torch.zeros(1, dtype=torch.float64, device=device)
+        nbytes = int(_lib.load().yolo_grad_sqnorm_workspace_bytes(self.n_chunks))
+        self.workspace = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=device)
+
+    def covers(self, *ts):
+        _chk_f32(*ts)
+        for t in ts:
+            if t is not None and t.numel() < self.extent:
+                raise YoloHipError(f"chunk table reaches element {self.extent}, the buffer has {t.numel()}")
+
+
+def _chk_hyper(hyper):
+    _chk_f32(hyper)
+    if hyper.numel() < OPT_HYPER:
+        raise YoloHipError(f"hyper needs {OPT_HYPER} floats, got {hyper.numel()}")
+
+
+def grad_sqnorm(g, table):
+    """table.var_sq[v] = sum of squares of variable v of `g` in double, table.total_sq = their ordered sum"""
+    table.covers(g)
+    ws = table.workspace
+    check(_lib.load().yolo_grad_sqnorm(_p(g), _p(table.off), _p(table.len), table.n_chunks, _p(table.first), table.n_vars,
+                                       _p(table.var_sq), _p(table.total_sq), _p(ws), ws.numel() * ws.element_size(),
+                                       _stream()), "yolo_grad_sqnorm")
+
+
+def clip_factors(table, hyper, mode, factors, norm_out=None, extra=None):
+    """clip factors from table's norms (after grad_sqnorm): mode CLIP_NORM -> factors[v] per variable, CLIP_GLOBAL ->
+    factors[0]; the global norm also counts `extra.total_sq` (a second table: the trainable anchors) and goes to norm_out"""
+    _chk_hyper(hyper)
+    _chk_f32(factors, norm_out)
+    if mode not in (CLIP_NORM, CLIP_GLOBAL) or factors.numel() < (table.n_vars if mode == CLIP_NORM else 1):
+        raise YoloHipError("clip_factors: bad mode or too few factors")
+    check(_lib.load().yolo_clip_factors(_p(table.var_sq), table.n_vars, _p(table.total_sq),
+                                        _p(extra.total_sq if extra is not None else None), _p(hyper), int(mode),
+                                        _p(factors), _p(norm_out), _stream()), "yolo_clip_factors")
+
+
+def _chk_clip(table, mode, factors):
+    if mode in (CLIP_NORM, CLIP_GLOBAL):
+        _chk_f32(factors)
+        if factors is None or factors.numel() < (table.n_vars if mode == CLIP_NORM else 1):
+            raise YoloHipError("clipping by norm needs its factors (clip_factors)")
+    elif mode not in (CLIP_NONE, CLIP_VALUE):
+        raise YoloHipError(f"bad clip mode {mode}")
+
+
+def adam_step_clip(p, g, m, v, table, hyper, factors=None, clip_mode=CLIP_NONE, vhat=None, zero_grad=True):
+    """Adam over the variables of `table` on the clipped gradient, every scalar from `hyper`; vhat: the AMSGrad slot"""
+    table.covers(p, g, m, v, vhat)
+    _chk_hyper(hyper)
+    _chk_clip(table, clip_mode, factors)
+    check(_lib.load().yolo_adam_step_clip(_p(p), _p(g), _p(m), _p(v), _p(vhat), _p(table.off), _p(table.len), _p(table.var),
+                                          table.n_chunks, _p(hyper), _p(factors), int(clip_mode), int(bool(zero_grad)),
+                                          _stream()), "yolo_adam_step_clip")
+
+
+def sgd_step_clip(p, g, table, hyper, accum=None, nesterov=False, factors=None, clip_mode=CLIP_NONE, zero_grad=True):
+    """Keras SGD over the variables of `table` on the clipped gradient; accum: the momentum slot (None: no momentum)"""
+    table.covers(p, g, accum)
+    _chk_hyper(hyper)
+    _chk_clip(table, clip_mode, factors)
+    if nesterov and accum is None:
+        raise YoloHipError("sgd_step_clip: nesterov needs the momentum accumulator")
+    check(_lib.load().yolo_sgd_step_clip(_p(p), _p(g), _p(accum), int(bool(nesterov)), _p(table.off), _p(table.len),
+                                         _p(table.var), table.n_chunks, _p(hyper), _p(factors), int(clip_mode),
+                                         int(bool(zero_grad)), _stream()), "yolo_sgd_step_clip")
+
+
 def decode_level(pred, A, C, version, threshold, rows, max_rows, count, workspace):
     gh, gw = pred.shape[0], pred.shape[1]
     lib = _lib.load()
