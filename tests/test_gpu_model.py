@@ -739,7 +739,7 @@ def test_planes_path_agrees_with_exact_kernels_at_full_layer_sizes():
 @pytest.mark.parametrize("version", [3, 4])
 def test_fused_bn_backward_reduction_option_gives_the_same_gradients(version, monkeypatch):
     """YOLO_BN_FUSED_REDUCE=1 (the BatchNormalization-backward sums made by the data gradient that completes dL/d(a):
-    engine._plan_fused_reduce, include/yolo_hip.h: yolo_conv2d_dgrad_planes_bnred) against the default (standalone
+    plan._plan_fused_reduce, include/yolo_hip.h: yolo_conv2d_dgrad_planes_bnred) against the default (standalone
     reduction): same weights, same batch, one forward + loss + backward. Every parameter gradient within 2e-5 of the
     largest gradient of its tensor (fp32 tile sums folded in fp64 against per-element fp64 accumulation; split-K data
     gradients run unsplit in the fused form), the losses equal, and the fused form actually in use."""

@@ -19,18 +19,15 @@ libyolo_hip.so on the current stream. Design points (MI355X-first, see DESIGN.md
 import math
 
 import contextlib
-import os
 
 import numpy as np
 import torch
 
 from . import ops
+from . import plan
 from . import tape
 from ._lib import ACT_LEAKY, ACT_LINEAR, ACT_MISH, YoloHipError
-
-# words of the bounds / tickets block of a conv unit in Network._aux (zeroed at the start of every forward pass): [0] bound of the
-# BatchNorm output, [1..68] the 68 words of yolo_bn_act_bwd_reduce_bound, [69..104] ticket words of its in-launch fold
-AUX_WORDS = 112
+from .plan import AUX_WORDS, has_filter
 
 ACT_NAMES = {ACT_LINEAR: "linear", ACT_LEAKY: "leaky", ACT_MISH: "mish"}
 
@@ -120,6 +117,7 @@ class TensorRef:
 
 class Unit:
     kind = "unit"
+    residual = None
 
     def __init__(self, name):
         self.name = name
@@ -146,10 +144,15 @@ class HeadUnit(Unit):
     """All per-anchor 1x1 head convs of one output level fused into one [A*(5+C)] x Cin GEMM
     plus the per-channel activations (yolov3/models/__init__.py:40-65)."""
     kind = "head"
+    k = stride = 1      # the questions a ConvUnit answers, for code that treats both alike
+    padding = "same"
+    bn = False
+    bias = True
 
     def __init__(self, name, src, A, C, version, anchors, level, kernel_init):
         super().__init__(name)
         self.src, self.A, self.C, self.version, self.level = src, A, C, version, level
+        self.cout = (5 * A + C) if version == 1 else A * (5 + C)
         self.kernel_init = kernel_init
         self.anchors = [tuple(map(float, a)) for a in anchors] if anchors is not None else None
         self.inputs = [src]
@@ -244,8 +247,8 @@ class GraphBuilder:
         return self._push(SpaceToDepthUnit(name, src), src.h // 2, src.w // 2, src.c * 4)
 
     def head(self, src, A, C, version, anchors, name, level):
-        cout = (5 * A + C) if version == 1 else A * (5 + C)
-        out = self._push(HeadUnit(name, src, A, C, version, anchors, level, self.kernel_init), src.h, src.w, cout)
+        u = HeadUnit(name, src, A, C, version, anchors, level, self.kernel_init)
+        out = self._push(u, src.h, src.w, u.cout)
         self.outputs.append(out)
         return out
 
@@ -254,11 +257,9 @@ def count_params(builder):
     """(trainable, non_trainable) parameter counts of a built graph (no device needed)."""
     train = state = 0
     for u in builder.units:
-        if u.kind == "conv":
+        if has_filter(u):
             train += u.cout * u.k * u.k * u.src.c + (u.cout if u.bias else 0) + (2 * u.cout if u.bn else 0)
             state += 2 * u.cout if u.bn else 0
-        elif u.kind == "head":
-            train += u.out.c * u.src.c + u.out.c
     return train, state
 
 
@@ -266,16 +267,22 @@ def conv_flops_per_image(builder):
     """2*Ho*Wo*Cout*Cin*kh*kw summed over every conv (head convs included): SURVEY.md section 8d."""
     total = 0
     for u in builder.units:
-        if u.kind == "conv":
+        if has_filter(u):
             total += 2 * u.out.h * u.out.w * u.cout * u.src.c * u.k * u.k
-        elif u.kind == "head":
-            total += 2 * u.out.h * u.out.w * u.out.c * u.src.c
     return total
 
 
 # --------------------------------------------------------------------------------------------
 # runtime
 # --------------------------------------------------------------------------------------------
+_EPILOGUES = {ACT_LEAKY: ops.EPI_AFFINE_LEAKY, ACT_MISH: ops.EPI_AFFINE_MISH}
+
+
+def _epilogue(u):
+    """the fused-epilogue code of a conv + BN unit's inference form: folded BatchNormalization + its activation"""
+    return _EPILOGUES.get(u.act, ops.EPI_AFFINE)
+
+
 class Network:
     def __init__(self, builder, device="cuda", seed=1234, unbiased_moving_var=True):
         if not torch.cuda.is_available():
@@ -290,6 +297,15 @@ class Network:
         self.input = builder.input
         self.outputs = list(builder.outputs)
         self.unbiased_moving_var = unbiased_moving_var
+        # the switches (plan.Options says what each one does) as _overlap_wgrad, _prep_beside, _stem_fused, _bn_tight,
+        # _res_from_planes, _use_infer_graph, _fuse_infer, _concat_grad_slices, _dyp_per_layer, _bn_fold, _bn_fused_reduce,
+        # _pool_fuse, _concat_planes, _infer_onepass, _infer_small_fuse; _overlap_wgrad is read at every call (bench.py sets it)
+        self._opts = plan.Options.from_env()
+        for k, v in vars(self._opts).items():
+            setattr(self, "_" + k, v)
+        g = self._plan = plan.plan_graph(self.units, self.tensors, self.input, self.outputs, self._opts)
+        self._needs_grad, self._n_consumers = g.needs_grad, g.n_consumers
+        self._bound_alias, self._up_producer = g.bound_alias, g.up_producer
         self.params = ParamStore()   # trainable
         self.state = ParamStore()    # BN moving statistics (not trainable, not all-reduced)
         self._declare_params()
@@ -297,23 +313,49 @@ class Network:
         self.params.materialize(self.device, rng)
         self.state.materialize(self.device, rng)
         self.grads = torch.zeros_like(self.params.data)
-        self._wT = torch.empty(self._wT_total, device=self.device, dtype=torch.float32)
-        self._wT_valid = False
-        self._overlap_wgrad = os.environ.get("YOLO_BWD_OVERLAP", "1") != "0"
-        self._prep_beside = os.environ.get("YOLO_PREP_OVERLAP", "1") != "0"   # filter preparation beside the stem
-        self._stem_fused = os.environ.get("YOLO_STEM_FUSED_BWD", "1") != "0"  # stem: BN backward apply + wgrad in one pass
-        self._bn_tight = int(os.environ.get("YOLO_BN_TIGHT_BOUND", "0"))
-        self._res_from_planes = os.environ.get("YOLO_RES_PLANES", "1") != "0"  # residual adds read the planes, not an fp32 copy
+        self._init_anchors()
+        ops.create_side_streams(self.device)   # this device's filter-gradient / communication streams (fixed creation order)
+        ops.ensure_conv_workspace()   # scratch of the persistent (stream-K) window kernel: small-batch launches
+        ops.ensure_wgrad_workspace()  # slabs of the atomics-free filter / bias gradient reductions
+        self._alloc_planned_buffers(g)
+        self._wT_valid = self._wp_valid = self._wTp_valid = False
+        self._jobs_wp = self._jobs_wTp = self._jobs_wT = None
         self._wp_event = self._wT_event = None
-        self._use_infer_graph = os.environ.get("YOLO_INFER_GRAPH", "1") != "0"
-        self._fuse_infer = os.environ.get("YOLO_INFER_FUSE", "1") != "0"
         self._infer_graphs = {}
         self._wgrad_stream = None
         self._wgrad_pending = False
-        self._bn_f32 = torch.zeros(max(self._bn_f32_total, 1), device=self.device, dtype=torch.float32)
-        self._bn_f64 = torch.zeros(max(self._bn_f64_total, 1), device=self.device, dtype=torch.float64)
-        # head anchors (v2-v4): views into ONE flat buffer with a gradient twin, so that trainable anchors
-        # (yolov4/__init__.py:147-159) are one more small optimizer tensor
+        self.batch = None
+        self.act = {}
+        self.training = False
+        self.grad_ready_hook = None   # called as hook(unit) after a unit's parameter grads are enqueued
+        self.backward_begin_hook = None   # called at the start of backward (the gradient reducer's time origin)
+        self._infer_scale_valid = False
+        # A one-pass inference unit leaves the bound of its result as one word per workgroup of its last launch (their
+        # maximum; include/yolo_hip.h: yolo_conv2d_fwd_infer_unit): _tword_n[tid] words of the tensor's row, allocated on first use
+        self._twords = None
+        self._tword_n = {}
+        self._xplanes_infer = {}
+        for u in self.units:
+            u.concat_reads_through = False
+
+    # ---- construction -------------------------------------------------------------------
+    def _declare_params(self):
+        for u in self.units:
+            if u.kind == "conv":
+                u.p_kernel = self.params.add(f"{u.name}_conv/kernel", (u.cout, u.k, u.k, u.src.c), u.kernel_init)
+                u.p_bias = self.params.add(f"{u.name}_conv/bias", (u.cout,), init_zeros) if u.bias else None
+                if u.bn:
+                    u.p_gamma = self.params.add(f"{u.name}_bn/gamma", (u.cout,), init_ones)
+                    u.p_beta = self.params.add(f"{u.name}_bn/beta", (u.cout,), init_zeros)
+                    u.s_mean = self.state.add(f"{u.name}_bn/moving_mean", (u.cout,), init_zeros)
+                    u.s_var = self.state.add(f"{u.name}_bn/moving_variance", (u.cout,), init_ones)
+            elif u.kind == "head":
+                u.p_kernel = self.params.add(f"{u.name}/kernel", (u.cout, 1, 1, u.src.c), u.kernel_init)
+                u.p_bias = self.params.add(f"{u.name}/bias", (u.cout,), init_zeros)
+
+    def _init_anchors(self):
+        """head anchors (v2-v4): views into ONE flat buffer with a gradient twin, so that trainable anchors
+        (yolov4/__init__.py:147-159) are one more small optimizer tensor"""
         self._anchors_dev, self._anchor_grad_views = {}, {}
         heads = [u for u in self.units if u.kind == "head" and u.anchors is not None]
         n_anch = sum(2 * len(u.anchors) for u in heads)
@@ -328,262 +370,38 @@ class Network:
             self._anchor_grad_views[u.name] = self.anchor_grads[off:off + n]
             off += n
         self.has_anchors = n_anch > 0
-        self.batch = None
-        self.act = {}
-        self.training = False
-        self.grad_ready_hook = None   # called as hook(unit) after a unit's parameter grads are enqueued
-        self.backward_begin_hook = None   # called at the start of backward (the gradient reducer's time origin)
-        self._infer_scale_valid = False
-        ops.create_side_streams(self.device)   # this device's filter-gradient / communication streams (fixed creation order)
-        ops.ensure_conv_workspace()   # scratch of the persistent (stream-K) window kernel: small-batch launches
-        ops.ensure_wgrad_workspace()  # slabs of the atomics-free filter / bias gradient reductions
-        # consumers per tensor decide whether a tensor needs a gradient at all
-        self._needs_grad = self._compute_needs_grad()
-        self._n_consumers = {}
+
+    def _alloc_planned_buffers(self, g):
+        """the flat buffers whose layout plan.plan_graph made, and each unit's constant views into them"""
+        dev = self.device
+        self._wT = torch.empty(g.wT_total, device=dev, dtype=torch.float32)
+        self._bn_f32 = torch.zeros(max(g.bn_f32_total, 1), device=dev, dtype=torch.float32)
+        self._bn_f64 = torch.zeros(max(g.bn_f64_total, 1), device=dev, dtype=torch.float64)
+        self._bn_stats_total = g.bn_stats_total
+        self._wplanes = torch.empty(g.wplanes_total, device=dev, dtype=torch.uint8) if g.wplanes_total else None
+        self._aux = torch.zeros(g.aux_total, device=dev, dtype=torch.int32)
+        self._tbound = self._aux[g.tbound_off:].view(torch.float32)
+        self._tb = [self._tbound[i:i + 1] for i in range(len(self.tensors))]   # a tensor's bound float
+        self._pred = torch.zeros(g.pred_total, device=dev, dtype=torch.float32)
         for u in self.units:
-            for t in u.inputs:
-                self._n_consumers[t.tid] = self._n_consumers.get(t.tid, 0) + 1
-        for t in self.outputs:
-            self._n_consumers[t.tid] = self._n_consumers.get(t.tid, 0) + 1
-        # the gradient of a Concatenate reaches the BatchNormalization backward of its sources as a channel SLICE of the
-        # concat's gradient (ops.ChannelSlice: read in place with its row pitch) instead of being copied out per source
-        self._concat_grad_slices = os.environ.get("YOLO_CONCAT_GRAD_SLICE", "1") != "0"
-        self._dyp_per_layer = os.environ.get("YOLO_DYP_PER_LAYER", "1") != "0"
-        # round 6: YOLO_BN_FOLD=1 finishes the BatchNormalization-backward reduction inside its own launch
-        # (yolo_bn_act_bwd_reduce_fold_ld: the last workgroups to arrive fold the slots) instead of a bn_bwd_sum launch per
-        # layer: 72 launches fewer. Default 0: measured neutral on YOLOv3-416 (28.99 / 28.99 ms) and 1 % SLOWER on YOLOv4-608
-        # (37.20 -> 37.56: profiles/r06_a_bn_fold_ab_*.log) -- the two dependent memory-side round trips of the fold's tail
-        # cost what the 8 us launch cost behind a queue that dispatches back to back
-        self._bn_fold = os.environ.get("YOLO_BN_FOLD", "0") == "1"
-        # The BatchNormalization-backward reduction of a conv + BN unit P (sums of dz and dz * xhat over dL/d(P.out)) is made
-        # by the data gradient that COMPLETES dL/d(P.out) -- the last contribution in backward order, when that is a planes
-        # data gradient (include/yolo_hip.h: yolo_conv2d_dgrad_planes_bnred): W.bnred_for = P on that writer W.
-        # YOLO_BN_FUSED_REDUCE: 0 never, 1 every planes data gradient that completes a tensor, or a set of writer classes
-        # "w" (3x3 stride-1 with enough tiles to run unsplit), "s" (stride 2), "p" (1x1), "h" (heads), "t" (the small
-        # 3x3 layers that lose their split-K), e.g. "ws"
-        # Default 0: measured (profiles/r05_a_*): the step does not get shorter with it -- the y tile costs the data gradient as
-        # much as the standalone pass cost beside the filter-gradient stream.
-        self._bn_fused_reduce = os.environ.get("YOLO_BN_FUSED_REDUCE", "0")
-        self._plan_fused_reduce()
-        # pre-split ("planes") copies of the filters for the LDS-DMA conv kernels: [Cout][taps*Cin] for
-        # forward, [Cin][taps*Cout] for dgrad; refreshed when the parameters change
-        wp = 0
-        for u in self.units:
-            if u.kind not in ("conv", "head"):
+            a = u.aux_off
+            u.bound = self._aux[a:a + 1]             # bound of the BatchNorm output
+            u.red_bound = self._aux[a + 1:a + 69]    # the 68 words of yolo_bn_act_bwd_reduce_bound
+            u.tickets = self._aux[a + 69:a + 69 + ops.BN_FOLD_TICKET_WORDS]
+            u.pred = self._pred[u.pred_off:u.pred_off + 2]
+            if u.kind == "conv" and u.bn:
+                u.amax = self._aux[a + AUX_WORDS:a + AUX_WORDS + u.cout]   # per-channel max|conv out|
+            if not has_filter(u):
                 continue
-            cout = u.cout if u.kind == "conv" else u.out.c
-            k = u.k if u.kind == "conv" else 1
-            u.planes_fwd = ops.planes_fwd_ok(u.src.c, cout)
-            u.planes_dgrad = ops.planes_dgrad_ok(u.src.c, cout) and self._needs_grad[u.src.tid]
-            u.planes_wgrad = u.planes_fwd and ops.planes_wgrad_ok(u.src.c, cout, k * k, u.stride if u.kind == "conv" else 1)
-            u.wp_off = u.wTp_off = -1
-            # heads whose channel count is not a multiple of 16 (YOLOv3: 255): the backward kernels run on the
-            # channel count rounded up to 16 - head gradient planes with zero columns, filters with zero rows
-            u.cpad = 0
-            if (u.kind == "head" and cout % 16 != 0 and not u.planes_dgrad
-                    and os.environ.get("YOLO_HEAD_PAD", "1") != "0"):
-                cp = (cout + 15) // 16 * 16
-                if u.planes_fwd and ops.planes_wgrad_ok(u.src.c, cp, 1) and ops.planes_dgrad_ok(u.src.c, cp):
-                    u.cpad = cp
-                    u.wTp_pad_off, u.wTp_pad_bytes = wp, ops.planes_bytes(u.src.c, cp)
-                    wp += (u.wTp_pad_bytes + 255) // 256 * 256
-            if u.planes_fwd:
-                u.wp_off, u.wp_bytes = wp, ops.planes_bytes(cout, k * k * u.src.c)
-                wp += (u.wp_bytes + 255) // 256 * 256
-            if u.planes_dgrad:
-                u.wTp_off, u.wTp_bytes = wp, ops.planes_bytes(u.src.c, k * k * cout)
-                wp += (u.wTp_bytes + 255) // 256 * 256
-        self._wplanes = torch.empty(wp, device=self.device, dtype=torch.uint8) if wp else None
-        for u in self.units:
-            if u.kind == "head" and u.cpad:
+            u.wT = self._wT[u.wT_off:u.wT_off + u.cout * u.k * u.k * u.src.c]
+            u.wp = self._wplanes[u.wp_off:u.wp_off + u.wp_bytes] if u.planes_fwd else None
+            u.wTp = self._wplanes[u.wTp_off:u.wTp_off + u.wTp_bytes] if u.planes_dgrad else None
+            if u.cpad:
+                u.wTp_pad = self._wplanes[u.wTp_pad_off:u.wTp_pad_off + u.wTp_pad_bytes]
                 n = u.cpad * u.src.c
-                u.w_pad = torch.zeros(n, device=self.device, dtype=torch.float32)    # [cpad][cin], zero rows past out.c
-                u.wT_pad = torch.empty(n, device=self.device, dtype=torch.float32)   # [cin][cpad]
-                u.dw_pad = torch.empty(n, device=self.device, dtype=torch.float32)   # filter-gradient scratch
-        # fp32 copy of a BN/activation output is skipped (training) when every consumer is a conv that reads the
-        # planes for both its forward and its filter gradient
-        consumers = {}
-        for u in self.units:
-            for t in u.inputs:
-                consumers.setdefault(t.tid, []).append(u)
-        out_tids = {t.tid for t in self.outputs}
-        for u in self.units:
-            if u.kind == "conv":
-                cs = consumers.get(u.out.tid, [])
-                # the fp32 copy of a conv unit's output is written in training only if somebody reads it: consumers that take
-                # it as a planes operand (planes conv / head units) do not, nor do conv + BN units that ADD it as their
-                # residual (bn_act_fwd reads the residual from the planes too, yolo_bn_act_fwd_res_planes)
-                def reads_planes_only(c):
-                    if c.kind in ("conv", "head") and c.src.tid == u.out.tid and getattr(c, "residual", None) is not u.out:
-                        return c.planes_fwd and c.planes_wgrad
-                    return (self._res_from_planes and c.kind == "conv" and c.bn and getattr(c, "residual", None) is u.out
-                            and c.src.tid != u.out.tid and c.cout % 16 == 0)
-                has_planes_src = any(c.kind in ("conv", "head") and c.src.tid == u.out.tid and c.planes_fwd for c in cs)
-                u.a_needed = ((not cs) or (u.out.tid in out_tids) or u.cout % 16 != 0 or not has_planes_src
-                              or any(not reads_planes_only(c) for c in cs))
-        # conv + BN + activation units whose ONLY consumer is a 2x2 / stride-2 pool that tiles their output (Darknet-19,
-        # tiny-YOLOv3): in training the BatchNorm apply, the pool and the planes of the pooled tensor are ONE launch
-        # (yolo_bn_act_maxpool2x2_fwd) and the unpooled activation is never written (YOLO_POOL_FUSE=0: three launches)
-        self._pool_fuse = os.environ.get("YOLO_POOL_FUSE", "1") != "0"
-        for u in self.units:
-            u.pool_fuse = None
-        if self._pool_fuse:
-            for u in self.units:
-                if u.kind != "conv" or not u.bn or u.residual is not None or u.out.tid in out_tids:
-                    continue
-                cs = consumers.get(u.out.tid, [])
-                if len(cs) != 1 or cs[0].kind != "maxpool":
-                    continue
-                p = cs[0]
-                if (p.k == 2 and p.stride == 2 and u.out.h % 2 == 0 and u.out.w % 2 == 0 and p.out.h * 2 == u.out.h
-                        and p.out.w * 2 == u.out.w and u.cout % 8 == 0 and p.padding in ("same", "valid")):
-                    pcs = consumers.get(p.out.tid, [])
-                    p.f32_needed = (p.out.tid in out_tids) or (not pcs) or p.out.c % 16 != 0 or any(
-                        not (c.kind in ("conv", "head") and c.src.tid == p.out.tid and c.planes_fwd and c.planes_wgrad
-                             and getattr(c, "residual", None) is not p.out) for c in pcs)
-                    u.pool_fuse = p
-        # concat units write the planes of their result directly from the fp32 sources (yolo_split_planes_concat): the fp32
-        # concatenation is produced only if somebody other than a planes convolution reads it; a source's bound is the one
-        # its producer recorded -- BatchNorm's output bound, or, through pools / upsampling / space-to-depth (which cannot
-        # increase max|x|), their input's
-        self._concat_planes = os.environ.get("YOLO_CONCAT_PLANES", "1") != "0"
-        self._bound_alias = {}
-        for u in self.units:
-            if u.kind in ("upsample", "maxpool", "space_to_depth"):
-                self._bound_alias[u.out.tid] = self._bound_alias.get(u.src.tid, u.src.tid)
-            elif u.kind == "concat":
-                cs = consumers.get(u.out.tid, [])
-                u.f32_needed = (u.out.tid in out_tids) or (not cs) or any(
-                    not (c.kind in ("conv", "head") and c.src.tid == u.out.tid and c.planes_fwd and c.planes_wgrad
-                         and getattr(c, "residual", None) is not u.out) for c in cs)
-        self._wp_valid = False
-        self._wTp_valid = False
-        self._jobs_wp = self._jobs_wTp = self._jobs_wT = None
-        # bounds for the planes scales (planes.hpp): 72 words per conv unit, zeroed every step; one float per
-        # tensor = bound of that activation
-        off = 0
-        for u in self.units:
-            u.aux_off = off       # [0] forward bound, [1..68] = the 68 words of yolo_bn_act_bwd_reduce_bound, [69..104] = the
-            off += AUX_WORDS      # ticket words of its in-launch fold, [AUX_WORDS .. +C) = per-channel max|conv out| (conv epilogue)
-            if u.kind == "conv" and u.bn:
-                off += (u.cout + 7) // 8 * 8
-        # (the per-tensor bounds live behind the units' words: zeroed with them at the start of every forward pass, which the
-        # one-pass inference units need -- their kernels raise the bound of their result with atomicMax)
-        ntb = max(len(self.tensors), 1) + 1
-        self._aux = torch.zeros(max(off, 1) + ntb, device=self.device, dtype=torch.int32)
-        self._tbound = self._aux[max(off, 1):].view(torch.float32)
-        # A one-pass inference unit leaves the bound of its result as one word per workgroup of its last launch (their
-        # maximum; include/yolo_hip.h: yolo_conv2d_fwd_infer_unit): _tword_n[tid] words of the tensor's row, allocated on first use
-        self._twords = None
-        self._tword_n = {}
-        # {K, D} of every conv-BN unit for the a-priori bound of its inference output (ops.conv_pred_bound): made with
-        # the folded scale / shift, i.e. once per set of weights
-        self._pred = torch.zeros(2 * max(len(self.units), 1), device=self.device, dtype=torch.float32)
-        for i, u in enumerate(self.units):
-            u.pred_off = 2 * i
-        self._infer_onepass = os.environ.get("YOLO_INFER_ONEPASS", "1") != "0"
-        # round 6, bs-1 predict (no launch of the replayed graph costs less than ~4.5 us: DESIGN.md section 3.10):
-        # (a) an UpSampling2D(2) whose only reader is a Concatenate is read THROUGH by the concat's planes pass (inference),
-        # which also takes the sources' bounds as the words the one-pass units left instead of a fold launch per source
-        # (yolo_split_planes_concat_ex); (b) a conv + BN unit nobody reads as planes (the FPN's lateral 1x1 in front of the
-        # upsampling) still runs as a one-pass unit into planes of its own that nobody reads -- one launch instead of four;
-        # (c) the heads: convolution + activation in one call (yolo_conv2d_fwd_head_unit). YOLO_INFER_SMALL_FUSE=0: off
-        self._infer_small_fuse = os.environ.get("YOLO_INFER_SMALL_FUSE", "1") != "0"
-        self._up_producer = {}
-        for u in self.units:
-            u.concat_reads_through = False
-            if u.kind == "upsample" and self._n_consumers.get(u.out.tid, 0) == 1 and u.out.tid not in out_tids:
-                cs = consumers.get(u.out.tid, [])
-                if (len(cs) == 1 and cs[0].kind == "concat" and u.out.h == 2 * u.src.h and u.out.w == 2 * u.src.w
-                        and u.out.c == u.src.c):
-                    self._up_producer[u.out.tid] = u
-        self._xplanes_infer = {}
-
-    # ---- construction -------------------------------------------------------------------
-    def _declare_params(self):
-        wT = 0
-        f32 = 0
-        f64 = 0
-        for u in self.units:
-            if u.kind == "conv":
-                cin = u.src.c
-                u.p_kernel = self.params.add(f"{u.name}_conv/kernel", (u.cout, u.k, u.k, cin), u.kernel_init)
-                u.p_bias = self.params.add(f"{u.name}_conv/bias", (u.cout,), init_zeros) if u.bias else None
-                if u.bn:
-                    u.p_gamma = self.params.add(f"{u.name}_bn/gamma", (u.cout,), init_ones)
-                    u.p_beta = self.params.add(f"{u.name}_bn/beta", (u.cout,), init_zeros)
-                    u.s_mean = self.state.add(f"{u.name}_bn/moving_mean", (u.cout,), init_zeros)
-                    u.s_var = self.state.add(f"{u.name}_bn/moving_variance", (u.cout,), init_ones)
-                    u.bn_f32_off = f32
-                    f32 += 4 * u.cout            # scale, shift, save_mean, save_invstd
-                    u.bn_f64_off = f64           # stats[SLOTS][2C]; all layers' statistics are contiguous: they are
-                    f64 += ops.BN_STAT_SLOTS * 2 * u.cout   # the part of the fp64 buffer that is zeroed every step
-                u.wT_off = wT
-                wT += u.cout * u.k * u.k * cin
-            elif u.kind == "head":
-                cin = u.src.c
-                cout = u.out.c
-                u.p_kernel = self.params.add(f"{u.name}/kernel", (cout, 1, 1, cin), u.kernel_init)
-                u.p_bias = self.params.add(f"{u.name}/bias", (cout,), init_zeros)
-                u.wT_off = wT
-                wT += cout * cin
-        self._bn_stats_total = f64
-        for u in self.units:              # red[RED_SLOTS+1][2C]: every slot is written before it is read, never zeroed
-            if u.kind == "conv" and u.bn:
-                u.bn_red_off = f64
-                f64 += (ops.BN_RED_SLOTS + 1) * 2 * u.cout
-        self._wT_total = wT
-        self._bn_f32_total = f32
-        self._bn_f64_total = f64
-
-    def _plan_fused_reduce(self):
-        """static walk of backward(): who contributes to dL/d(tensor), in which order. The last contributor of a tensor
-        produced by a conv + BatchNormalization unit P gets W.bnred_for = P if it is a conv / head unit (whether its data
-        gradient is a planes kernel is known later: _dgrad checks). A skipped writer (its own gradient never arrives) simply
-        never sets the flag P's backward looks for, and P makes the reduction itself."""
-        last = {}
-        for u in reversed(self.units):
-            u.bnred_for = None
-            if u.kind == "conv":
-                if u.bn and u.residual is not None and self._needs_grad[u.residual.tid]:
-                    last[u.residual.tid] = ("add", u)
-                if self._needs_grad[u.src.tid]:
-                    last[u.src.tid] = ("dgrad", u)
-            elif u.kind == "head":
-                if self._needs_grad[u.src.tid]:
-                    last[u.src.tid] = ("dgrad", u)
-            else:
-                for t in u.inputs:
-                    if self._needs_grad[t.tid]:
-                        last[t.tid] = ("other", u)
-        mode = self._bn_fused_reduce
-        if mode == "0":
-            return
-        for tid, (how, w) in last.items():
-            p = self.tensors[tid].producer
-            # (stride 2: the four parity classes of the data gradient must be ONE launch, csrc/conv.hip: dgrad_impl)
-            k, st = (w.k, w.stride) if w.kind == "conv" else (1, 1)
-            one_launch = st == 1 or (st == 2 and k == 3 and os.environ.get("YOLO_DGRAD_CLASSES", "1") != "0")
-            if not (how == "dgrad" and one_launch and p is not None and p.kind == "conv" and p.bn and p.cout % 4 == 0):
-                continue
-            if w.kind == "head":
-                cls = "h"
-            elif st == 2:
-                cls = "s"
-            elif k == 1:
-                cls = "p"
-            else:
-                cls = "w"
-            w.bnred_class = cls
-            if mode == "1" or cls in mode or (cls == "w" and "t" in mode):
-                w.bnred_for = p
-
-    def _compute_needs_grad(self):
-        needs = {self.input.tid: False}
-        for u in self.units:
-            has_params = u.kind in ("conv", "head")
-            needs[u.out.tid] = has_params or any(needs[t.tid] for t in u.inputs)
-        return needs
+                u.w_pad = torch.zeros(n, device=dev, dtype=torch.float32)    # [cpad][cin], zero rows past out.c
+                u.wT_pad = torch.empty(n, device=dev, dtype=torch.float32)   # [cin][cpad]
+                u.dw_pad = torch.empty(n, device=dev, dtype=torch.float32)   # filter-gradient scratch
 
     @property
     def num_params(self):
@@ -610,93 +428,51 @@ class Network:
         self.alloc_gen = getattr(self, "alloc_gen", 0) + 1   # captured step graphs (capture.py) belong to one allocation
         self._infer_graphs = {}   # captured graphs point into the buffers re-allocated below
         self.act = {}
-        dev = self.device
-        for u in self.units:
-            oh, ow, oc = u.out.h, u.out.w, u.out.c
-            if u.kind == "conv":
-                u.desc = ops.conv_desc((N, u.src.h, u.src.w, u.src.c), u.cout, u.k, u.k, u.stride, u.padding)
-                u.y = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.float32)
-                needs_a = u.bn or u.act != ACT_LINEAR
-                u.a = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.float32) if needs_a else u.y
-                self.act[u.out.tid] = u.a
-            elif u.kind == "head":
-                u.desc = ops.conv_desc((N, u.src.h, u.src.w, u.src.c), oc, 1, 1, 1, "same")
-                u.t = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.float32)
-                u.yact = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.float32)
-                self.act[u.out.tid] = u.yact
-            elif u.kind == "maxpool":
-                u.buf = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.float32)
-                u.argmax = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.int32)
-                if u.padding == "same":
-                    _, u.pad_t = ops.same_pad(u.src.h, u.k, u.stride)
-                    _, u.pad_l = ops.same_pad(u.src.w, u.k, u.stride)
-                else:
-                    u.pad_t = u.pad_l = 0
-                self.act[u.out.tid] = u.buf
-            else:
-                u.buf = torch.empty((N, oh, ow, oc), device=dev, dtype=torch.float32)
-                self.act[u.out.tid] = u.buf
-        # slots of the BatchNormalization-backward reductions made by data gradients (_plan_fused_reduce)
+        bp = plan.plan_batch(self.units, N, self._opts)
+
+        def new(u, dtype=torch.float32):
+            return torch.empty((N, u.out.h, u.out.w, u.out.c), device=self.device, dtype=dtype)
+
+        def new_bytes(n, make=torch.empty):
+            return make(n, device=self.device, dtype=torch.uint8)
         for u in self.units:
             u.bnred = None
-        for w in self.units:
-            p = getattr(w, "bnred_for", None)
-            if p is None or not (w.planes_dgrad or (w.kind == "head" and w.cpad)):
-                continue
+            if u.kind == "conv":
+                u.desc = bp.desc[u.name]
+                u.y = new(u)
+                u.a = new(u) if (u.bn or u.act != ACT_LINEAR) else u.y
+                self.act[u.out.tid] = u.a
+            elif u.kind == "head":
+                u.desc, u.desc_pad = bp.desc[u.name], bp.desc_pad.get(u.name)
+                u.t = new(u)
+                u.yact = new(u)
+                self.act[u.out.tid] = u.yact
+            else:
+                u.buf = new(u)
+                if u.kind == "maxpool":
+                    u.argmax = new(u, torch.int32)
+                    u.pad_t, u.pad_l = bp.pool_pad[u.name]
+                self.act[u.out.tid] = u.buf
+        # the BatchNormalization-backward reductions made by data gradients (plan: _plan_fused_reduce, plan_batch)
+        by_name = {u.name: u for u in self.units}
+        for name, cap in bp.bnred_cap.items():
+            p = by_name[name]
             scale, shift, smean, sinv, _, _ = self._bn_bufs(p)
-            if getattr(w, "bnred_class", "") == "w" and self._bn_fused_reduce != "1":
-                # 3x3 stride-1 launches of at most 256 tiles run split-K (csrc/conv_win.hip: conv_split_parts), which the
-                # fused form gives up: their own class "t"
-                small = -(-N * w.src.h * w.src.w // 128) * -(-w.src.c // 128) <= 256
-                if not (("t" if small else "w") in self._bn_fused_reduce):
-                    continue
-            cap = ops.bnred_slots_cap(w.desc)   # (a head with padded channels uses desc_pad: same pixels, same Cin)
-            if cap <= 0:
-                continue
             p.bnred = ops.BnReduce(p.y, scale, shift, smean, sinv, p.act,
-                                   torch.empty(cap * 2 * p.cout, device=dev, dtype=torch.float32), cap,
-                                   self._aux[p.aux_off + 1:p.aux_off + 69])
+                                   torch.empty(cap * 2 * p.cout, device=self.device, dtype=torch.float32), cap, p.red_bound)
             p.bnred_done = False
-        # planes of the activations that feed planes-capable convs (kept from forward for the filter
-        # gradient), one scratch for the planes of the current layer's dy in backward
-        self._xplanes = {}
+        # planes of the activations that feed planes-capable convs (kept from forward for the filter gradient)
+        self._xplanes = {tid: new_bytes(n, torch.zeros) for tid, n in bp.xplanes_bytes.items()}
         self._xplanes_infer = {}
-        dyp = 0
-        for u in self.units:
-            if u.kind not in ("conv", "head"):
-                continue
-            if u.planes_fwd and u.src.tid not in self._xplanes:
-                self._xplanes[u.src.tid] = torch.zeros(ops.planes_bytes(N * u.src.h * u.src.w, u.src.c), device=dev,
-                                                       dtype=torch.uint8)
-            if u.kind == "head" and u.cpad:
-                dyp = max(dyp, ops.planes_bytes(N * u.out.h * u.out.w, u.cpad))
-                u.desc_pad = ops.conv_desc((N, u.src.h, u.src.w, u.src.c), u.cpad, 1, 1, 1, "same")
-            elif u.planes_dgrad or u.planes_wgrad:
-                dyp = max(dyp, ops.planes_bytes(N * u.out.h * u.out.w, u.cout if u.kind == "conv" else u.out.c))
-        # (two scratch buffers, used alternately: the filter gradient of layer L may still be reading its dy
-        # planes on the second stream while layer L-1 produces its own)
-        # (not allocated when every planes layer owns its buffer, the default below: _next_dyp_buffer creates them on demand)
-        self._dyp_shared_bytes = dyp
-        self._dyplanes2 = ([None, None] if self._dyp_per_layer else
-                           [torch.empty(dyp, device=dev, dtype=torch.uint8) if dyp else None for _ in range(2)])
+        self._xp_valid = set()
+        # planes of the current layer's dy in backward: every planes layer owns its buffer (Options.dyp_per_layer), or
+        # two scratch buffers are used alternately: the filter gradient of layer L may still be reading its dy planes on the
+        # second stream while layer L-1 produces its own (with own buffers _next_dyp_buffer creates the pair on demand)
+        dyp = self._dyp_shared_bytes = bp.dyp_shared_bytes
+        self._dyplanes2 = [None, None] if self._dyp_per_layer else [new_bytes(dyp) if dyp else None for _ in range(2)]
         self._dyp_events = [None, None]
         self._dyp_idx = 0
-        # YOLO_DYP_PER_LAYER=1 (default): every layer has its OWN dy planes instead -- 288 GB of HBM make the reuse pointless
-        # (YOLOv3-416 at bs 32: +4.6 GB), and the reuse costs the compute stream a wait on the filter-gradient stream's event
-        # per layer: a barrier packet in its queue even when the event has long fired (2.4 us each, 75 per step, measured
-        # with scripts/hip_probe/event_gap_probe.cpp: profiles/r05_a_event_gap_probe.log) plus the event record on the side
-        # stream. Across steps the buffers are safe: backward joins the filter-gradient stream before it returns.
-        self._dyp_own = {}
-        if self._dyp_per_layer:
-            for u in self.units:
-                if u.kind == "head" and u.cpad:
-                    nb = ops.planes_bytes(N * u.out.h * u.out.w, u.cpad)
-                elif u.kind in ("conv", "head") and (u.planes_dgrad or u.planes_wgrad):
-                    nb = ops.planes_bytes(N * u.out.h * u.out.w, u.cout if u.kind == "conv" else u.out.c)
-                else:
-                    continue
-                self._dyp_own[u.name] = torch.empty(nb, device=dev, dtype=torch.uint8)
-        self._xp_valid = set()
+        self._dyp_own = {name: new_bytes(n) for name, n in bp.dyp_own_bytes.items()}
 
     def _tb_row(self, tid):
         if self._twords is None:
@@ -708,13 +484,13 @@ class Network:
         """the recorded bound of tensor tid as ONE device float (folds the words of a one-pass inference unit once)"""
         n = self._tword_n.pop(tid, 0)
         if n:
-            ops.fold_bound(self._tb_row(tid)[:n], self._tbound[tid:tid + 1])
-        return self._tbound[tid:tid + 1]
+            ops.fold_bound(self._tb_row(tid)[:n], self._tb[tid])
+        return self._tb[tid]
 
     def _tb_words(self, tid):
         """the recorded bound of tensor tid as the one-pass units take it: the words such a unit left, or one float"""
         n = self._tword_n.get(tid, 0)
-        return self._tb_row(tid)[:n] if n else self._tbound[tid:tid + 1]
+        return self._tb_row(tid)[:n] if n else self._tb[tid]
 
     def _xp(self, t):
         """planes of activation tensor t for this forward pass (split once, shared by all consumers)"""
@@ -724,17 +500,17 @@ class Network:
             self._xp_valid.add(t.tid)
         return buf
 
+    def _filter_units(self):
+        return filter(has_filter, self.units)
+
     def _refresh_wplanes(self):
         if self._wp_valid or self._wplanes is None:
             return
         if self._jobs_wp is None:   # one batched launch for the planes of every filter (pointers never change)
             self._jobs_wp = ops.BatchJobs("split", self.device)
-            for u in self.units:
-                if u.kind in ("conv", "head") and u.planes_fwd:
-                    cout = u.cout if u.kind == "conv" else u.out.c
-                    k = u.k if u.kind == "conv" else 1
-                    self._jobs_wp.add_split(self.params.view(u.p_kernel.name),
-                                            self._wplanes[u.wp_off:u.wp_off + u.wp_bytes], cout, k * k * u.src.c)
+            for u in self._filter_units():
+                if u.planes_fwd:
+                    self._jobs_wp.add_split(self.params.view(u.p_kernel.name), u.wp, u.cout, u.k * u.k * u.src.c)
         self._jobs_wp.run()
         self._wp_valid = True
 
@@ -744,27 +520,36 @@ class Network:
         self._refresh_wplanes()   # bound donors of the transposed filters
         if self._jobs_wTp is None:
             self._jobs_wTp = ops.BatchJobs("split", self.device)
-            for u in self.units:
-                if u.kind == "head" and u.cpad:
-                    self._jobs_wTp.add_split(u.wT_pad, self._wplanes[u.wTp_pad_off:u.wTp_pad_off + u.wTp_pad_bytes],
-                                             u.src.c, u.cpad)
-                elif u.kind in ("conv", "head") and u.planes_dgrad:
-                    cout = u.cout if u.kind == "conv" else u.out.c
-                    k = u.k if u.kind == "conv" else 1
-                    n = cout * k * k * u.src.c
-                    donor = self._wplanes[u.wp_off:u.wp_off + u.wp_bytes] if u.planes_fwd else None
-                    self._jobs_wTp.add_split(self._wT[u.wT_off:u.wT_off + n],
-                                             self._wplanes[u.wTp_off:u.wTp_off + u.wTp_bytes], u.src.c, k * k * cout,
-                                             bound_from=donor)
+            for u in self._filter_units():
+                if u.cpad:
+                    self._jobs_wTp.add_split(u.wT_pad, u.wTp_pad, u.src.c, u.cpad)
+                elif u.planes_dgrad:
+                    self._jobs_wTp.add_split(u.wT, u.wTp, u.src.c, u.k * u.k * u.cout, bound_from=u.wp)
         self._jobs_wTp.run()
         self._wTp_valid = True
 
-    def _conv_fwd(self, u, xin, w, bias, out, stats=None):
-        amax = self._aux[u.aux_off + AUX_WORDS:u.aux_off + AUX_WORDS + u.cout] if (stats is not None and self._tight_bound(u)) else None
+    def _refresh_wT(self):
+        if self._wT_valid:
+            return
+        if self._jobs_wT is None:
+            self._jobs_wT = ops.BatchJobs("transpose", self.device)
+            for u in self._filter_units():
+                if u.cpad:
+                    self._jobs_wT.add_transpose(u.w_pad, u.wT_pad, u.cpad, 1, u.src.c)
+                else:
+                    self._jobs_wT.add_transpose(self.params.view(u.p_kernel.name), u.wT, u.cout, u.k * u.k, u.src.c)
+        for u in self.units:
+            if u.kind == "head" and u.cpad:
+                tape.torch_op(lambda u=u: u.w_pad[:u.out.c * u.src.c].copy_(self.params.view(u.p_kernel.name).reshape(-1)))
+        self._jobs_wT.run()
+        self._wT_valid = True
+
+    def _conv_fwd(self, u, bias, out, stats=None, absmax=None):
+        """the forward convolution of a conv / head unit: from planes where the unit has them, else the exact fp32 kernel"""
         if u.planes_fwd:
-            return ops.conv2d_fwd_planes(u.desc, self._xp(u.src), self._wplanes[u.wp_off:u.wp_off + u.wp_bytes], bias,
-                                         out=out, stats=stats, absmax=amax)
-        return ops.conv2d_fwd(u.desc, xin, w, bias, out=out, stats=stats, absmax=amax)
+            return ops.conv2d_fwd_planes(u.desc, self._xp(u.src), u.wp, bias, out=out, stats=stats, absmax=absmax)
+        return ops.conv2d_fwd(u.desc, self.act[u.src.tid], self.params.view(u.p_kernel.name), bias, out=out, stats=stats,
+                              absmax=absmax)
 
     def _tight_bound(self, u):
         """whether the conv epilogue records per-channel max|y| for the bound of the BatchNorm output (YOLO_BN_TIGHT_BOUND:
@@ -780,6 +565,14 @@ class Network:
         nr = (ops.BN_RED_SLOTS + 1) * 2 * c
         return (b[0:c], b[c:2 * c], b[2 * c:3 * c], b[3 * c:4 * c], self._bn_f64[u.bn_f64_off:u.bn_f64_off + ns],
                 self._bn_f64[u.bn_red_off:u.bn_red_off + nr])
+
+    def _fold_infer_scale(self, u, scale, shift):
+        """the folded inference scale / shift of a conv + BN unit: made once per set of weights. True if it was made now"""
+        if self._infer_scale_valid:
+            return False
+        ops.bn_fold_inference(u.cout, self.params.view(u.p_gamma.name), self.params.view(u.p_beta.name),
+                              self.state.view(u.s_mean.name), self.state.view(u.s_var.name), scale, shift)
+        return True
 
     # ---- inference through a captured HIP graph ------------------------------------------------------------
     def infer(self, x):
@@ -830,17 +623,43 @@ class Network:
         if x.dtype != torch.float32 or not x.is_cuda:
             raise YoloHipError("forward expects a float32 CUDA tensor")
         x = x.contiguous()
-        N = x.shape[0]
         if tuple(x.shape[1:]) != (self.input.h, self.input.w, self.input.c):
             raise YoloHipError(f"input shape {tuple(x.shape[1:])} != model input "
                                f"{(self.input.h, self.input.w, self.input.c)}")
-        self.allocate(N)
+        self.allocate(x.shape[0])
         self.training = training
         self.act[self.input.tid] = x
         self._xp_valid = set()
         self._tbound_set = set()
         self._tword_n = {}        # tensors whose recorded bound is (still) the words of a one-pass inference unit
-        # (a pending event of an earlier forward stays until a planes conv / a backward has waited for it)
+        self._prepare_filters(training)
+        ops.zero_bytes(self._aux)   # bounds / per-channel maxima of this pass
+        if training:
+            ops.zero_bytes(self._bn_f64[:self._bn_stats_total])
+            self._infer_scale_valid = False  # moving statistics (and the shared scale/shift) change
+            # captured inference graphs were recorded with the folded scale/shift valid (no bn_fold_inference
+            # inside): a training-mode forward overwrites those buffers with batch statistics, so drop them
+            self._infer_graphs = {}
+        prev_name = None
+        for u in self.units:
+            if stop_after is not None and prev_name == stop_after:
+                self.training = False   # an incomplete pass: backward() must not run on it
+                return None
+            prev_name = u.name
+            if self._wp_event is not None and has_filter(u) and u.planes_fwd:
+                tape.wait_event(torch.cuda.current_stream(), self._wp_event)
+                self._wp_event = None
+            fwd = getattr(self, "_fwd_" + u.kind, None)
+            if fwd is None:
+                raise YoloHipError(f"unknown unit kind {u.kind}")
+            fwd(u, training)
+        if not training:
+            self._infer_scale_valid = True
+        return [self.act[t.tid] for t in self.outputs]
+
+    def _prepare_filters(self, training):
+        """the filters' planes for this pass; in training, beside the stem, with what backward needs
+        (a pending event of an earlier forward stays until a planes conv / a backward has waited for it)"""
         if training and self._overlap_wgrad and self._prep_beside and not (self._wp_valid and self._wT_valid and self._wTp_valid):
             # the filters' planes (needed by the first planes conv) and their transposed forms (needed by backward) are
             # made on the second stream while the stem runs: 0.45 ms of HBM-bound launches beside MFMA-bound ones
@@ -856,188 +675,152 @@ class Network:
                 self._wT_event = tape.record_event(side)
         else:
             self._refresh_wplanes()
-        ops.zero_bytes(self._aux)   # bounds / per-channel maxima of this pass
-        if training:
-            ops.zero_bytes(self._bn_f64[:self._bn_stats_total])
-            self._infer_scale_valid = False  # moving statistics (and the shared scale/shift) change
-            # captured inference graphs were recorded with the folded scale/shift valid (no bn_fold_inference
-            # inside): a training-mode forward overwrites those buffers with batch statistics, so drop them
-            self._infer_graphs = {}
-        P = self.params
-        prev_name = None
-        for u in self.units:
-            if stop_after is not None and prev_name == stop_after:
-                self.training = False   # an incomplete pass: backward() must not run on it
-                return None
-            prev_name = getattr(u, "name", None)
-            if self._wp_event is not None and u.kind in ("conv", "head") and u.planes_fwd:
-                tape.wait_event(torch.cuda.current_stream(), self._wp_event)
-                self._wp_event = None
-            if u.kind == "conv":
-                xin = self.act[u.src.tid]
-                w = P.view(u.p_kernel.name)
-                bias = P.view(u.p_bias.name) if u.p_bias is not None else None
-                if u.bn:
-                    scale, shift, smean, sinv, stats, _ = self._bn_bufs(u)
-                    gamma, beta = P.view(u.p_gamma.name), P.view(u.p_beta.name)
-                    if training:
-                        # a conv bias in front of BatchNormalization (YOLOv1.5 / v2) cancels in (y - mean): the convolution
-                        # runs WITHOUT it -- u.y, the statistics and the saved mean are those of the bias-free tensor, so a
-                        # large bias cannot eat the digits of var = E[y^2] - mean^2 -- and only the moving mean adds it back
-                        self._conv_fwd(u, xin, w, None, u.y, stats)
-                        ops.bn_finalize(stats, u.y.numel() // u.cout, u.cout, gamma, beta,
-                                        self.state.view(u.s_mean.name), self.state.view(u.s_var.name),
-                                        scale, shift, smean, sinv, unbiased=self.unbiased_moving_var,
-                                        bound=self._aux[u.aux_off:u.aux_off + 1],
-                                        absmax=(self._aux[u.aux_off + AUX_WORDS:u.aux_off + AUX_WORDS + u.cout]
-                                                if self._tight_bound(u) else None), mean_offset=bias)
-                    elif self._fuse_infer and self._fused_infer_unit(u, bias, gamma, beta, scale, shift):
-                        continue
-                    elif self._fuse_infer and self._infer_onepass and self._stem_infer_unit(u, xin, w, bias, gamma, beta, scale, shift):
-                        continue
-                    else:
-                        amax = self._aux[u.aux_off + AUX_WORDS:u.aux_off + AUX_WORDS + u.cout]
-                        if u.planes_fwd:
-                            ops.conv2d_fwd_planes(u.desc, self._xp(u.src), self._wplanes[u.wp_off:u.wp_off + u.wp_bytes],
-                                                  bias, out=u.y, absmax=amax)
-                        else:
-                            ops.conv2d_fwd(u.desc, xin, w, bias, out=u.y, absmax=amax)
-                        if not self._infer_scale_valid:
-                            ops.bn_fold_inference(u.cout, gamma, beta, self.state.view(u.s_mean.name),
-                                                  self.state.view(u.s_var.name), scale, shift)
-                        ops.bn_infer_bound(u.cout, scale, shift, amax, self._aux[u.aux_off:u.aux_off + 1])
-                    if training and u.pool_fuse is not None:
-                        # BatchNorm apply + activation + the 2x2 pool behind it + the pooled tensor's planes in one launch; the
-                        # unpooled activation is not written (its only reader would have been the pool)
-                        pu = u.pool_fuse
-                        ppl = self._xplanes.get(pu.out.tid) if pu.out.c % 16 == 0 else None
-                        tb = self._tbound
-                        ops.bn_act_maxpool2x2_fwd(u.y, u.cout, scale, shift, u.act, pu.argmax,
-                                                  out=pu.buf if (pu.f32_needed or ppl is None) else None, planes=ppl,
-                                                  bn_bound=self._aux[u.aux_off:u.aux_off + 1],
-                                                  out_bound=tb[pu.out.tid:pu.out.tid + 1])
-                        self._tbound_set.add(pu.out.tid)
-                        if ppl is not None:
-                            self._xp_valid.add(pu.out.tid)
-                        pu.fused_this_pass = True
-                        continue
-                    res = self.act[u.residual.tid] if u.residual is not None else None
-                    res_pl = None
-                    if (res is not None and training and self._res_from_planes and u.cout % 16 == 0
-                            and u.residual.tid in self._xp_valid and u.residual.tid in self._tbound_set):
-                        res_pl, res = self._xplanes[u.residual.tid], None   # (its fp32 copy may not have been written)
-                    # consumers that are planes-capable convs get their operand straight from this kernel; the scale
-                    # comes from the bound bn_finalize (training) / bn_infer_bound (inference) derived from the conv
-                    # epilogue's per-channel max|y|
-                    pl = self._xplanes.get(u.out.tid) if u.cout % 16 == 0 else None
-                    if u.residual is not None and u.residual.tid not in self._tbound_set:
-                        pl = None   # residual without a recorded bound: split its consumers' operand separately
-                    else:
-                        self._tbound_set.add(u.out.tid)
-                    tb = self._tbound
-                    ops.bn_act_fwd(u.y, u.cout, scale, shift, u.act, res, out=u.a, planes=pl,
-                                   want_out=not (training and pl is not None and not u.a_needed),
-                                   bn_bound=self._aux[u.aux_off:u.aux_off + 1],
-                                   residual_bound=self._tb_float(u.residual.tid) if res is not None else None,
-                                   out_bound=tb[u.out.tid:u.out.tid + 1], residual_planes=res_pl)
-                    if pl is not None:
-                        self._xp_valid.add(u.out.tid)
-                else:
-                    self._conv_fwd(u, xin, w, bias, u.y)
-                    if u.act != ACT_LINEAR:
-                        ops.act_fwd(u.y, u.act, out=u.a)
-                    if u.residual is not None:
-                        raise YoloHipError("residual without BN is not used by any reference graph")
-            elif u.kind == "head":
-                xin = self.act[u.src.tid]
-                if not training and self._infer_small_fuse and self._fuse_infer and u.planes_fwd:
-                    ops.conv2d_fwd_head_unit(u.desc, self._xp(u.src), self._wplanes[u.wp_off:u.wp_off + u.wp_bytes],
-                                             P.view(u.p_bias.name), u.A, u.C, u.version, self._anchors_dev.get(u.name),
-                                             u.t, u.yact)
-                    continue
-                self._conv_fwd(u, xin, P.view(u.p_kernel.name), P.view(u.p_bias.name), u.t)
-                ops.head_act_fwd(u.t, u.A, u.C, u.version, self._anchors_dev.get(u.name), out=u.yact)
-            elif u.kind == "upsample":
-                if (not training and self._infer_small_fuse and self._concat_planes
-                        and u.out.tid in self._up_producer):
-                    u.concat_reads_through = True   # (the Concatenate behind it reads the half-size tensor itself)
-                    continue
-                ops.upsample2x_fwd(self.act[u.src.tid], u.buf, u.out.c, 0)
-            elif u.kind == "concat":
-                pl = self._xplanes.get(u.out.tid) if self._concat_planes else None
-                slots = [self._bound_alias.get(s.tid, s.tid) for s in u.srcs]
-                ups = [self._up_producer.get(s.tid) for s in u.srcs]
-                ups = [p if (p is not None and p.concat_reads_through) else None for p in ups]
-                if (pl is not None and len(u.srcs) <= 4 and all(sl in self._tbound_set for sl in slots)
-                        and all(s.c % 8 == 0 for s in u.srcs)):
-                    tb = self._tbound
-                    if any(p is not None for p in ups):
-                        ops.split_planes_concat_ex([self.act[p.src.tid] if p is not None else self.act[s.tid]
-                                                    for s, p in zip(u.srcs, ups)], [s.c for s in u.srcs],
-                                                   [self._tb_words(sl) for sl in slots], self.batch * u.out.h * u.out.w, pl,
-                                                   upsample=[p is not None for p in ups], hw=(u.out.h, u.out.w),
-                                                   dst32=u.buf if u.f32_needed else None,
-                                                   out_bound=tb[u.out.tid:u.out.tid + 1])
-                        for p in ups:
-                            if p is not None:
-                                p.concat_reads_through = False
-                    else:
-                        ops.split_planes_concat([self.act[s.tid] for s in u.srcs], [s.c for s in u.srcs],
-                                                [self._tb_float(sl) for sl in slots], self.batch * u.out.h * u.out.w, pl,
-                                                dst32=u.buf if u.f32_needed else None,
-                                                out_bound=tb[u.out.tid:u.out.tid + 1])
-                    self._xp_valid.add(u.out.tid)
-                    self._tbound_set.add(u.out.tid)
-                    continue
-                for p in ups:   # (this Concatenate cannot read through after all: make the upsampled tensors now)
-                    if p is not None:
-                        ops.upsample2x_fwd(self.act[p.src.tid], p.buf, p.out.c, 0)
-                        p.concat_reads_through = False
-                off = 0
-                for s in u.srcs:
-                    ops.copy_channels_in(self.act[s.tid], s.c, u.buf, u.out.c, off)
-                    off += s.c
-            elif u.kind == "maxpool":
-                if getattr(u, "fused_this_pass", False):   # made by its producer's BatchNorm launch (pool_fuse)
-                    u.fused_this_pass = False
-                    continue
-                ops.maxpool_fwd(self.act[u.src.tid], u.k, u.stride, u.pad_t, u.pad_l, u.out.h, u.out.w, u.buf,
-                                u.out.c, 0, u.argmax if training else None)
-            elif u.kind == "space_to_depth":
-                ops.space_to_depth2_fwd(self.act[u.src.tid], u.buf, u.out.c, 0)
-            else:
-                raise YoloHipError(f"unknown unit kind {u.kind}")
-        if not training:
-            self._infer_scale_valid = True
-        return [self.act[t.tid] for t in self.outputs]
 
-    def _stem_infer_unit(self, u, xin, w, bias, gamma, beta, scale, shift):
+    def _fwd_conv(self, u, training):
+        bias = self.params.view(u.p_bias.name) if u.p_bias is not None else None
+        if not u.bn:
+            self._conv_fwd(u, bias, u.y)
+            if u.act != ACT_LINEAR:
+                ops.act_fwd(u.y, u.act, out=u.a)
+            if u.residual is not None:
+                raise YoloHipError("residual without BN is not used by any reference graph")
+            return
+        scale, shift, smean, sinv, stats, _ = self._bn_bufs(u)
+        if training:
+            # a conv bias in front of BatchNormalization (YOLOv1.5 / v2) cancels in (y - mean): the convolution
+            # runs WITHOUT it -- u.y, the statistics and the saved mean are those of the bias-free tensor, so a
+            # large bias cannot eat the digits of var = E[y^2] - mean^2 -- and only the moving mean adds it back
+            amax = u.amax if self._tight_bound(u) else None
+            self._conv_fwd(u, None, u.y, stats, amax)
+            ops.bn_finalize(stats, u.y.numel() // u.cout, u.cout, self.params.view(u.p_gamma.name),
+                            self.params.view(u.p_beta.name), self.state.view(u.s_mean.name), self.state.view(u.s_var.name),
+                            scale, shift, smean, sinv, unbiased=self.unbiased_moving_var, bound=u.bound, absmax=amax,
+                            mean_offset=bias)
+            if u.pool_fuse is not None:
+                return self._fwd_bn_act_pool(u, scale, shift)
+        elif self._fuse_infer and (self._fused_infer_unit(u, bias, scale, shift)
+                                   or (self._infer_onepass and self._stem_infer_unit(u, bias, scale, shift))):
+            return
+        else:
+            self._conv_fwd(u, bias, u.y, absmax=u.amax)
+            self._fold_infer_scale(u, scale, shift)
+            ops.bn_infer_bound(u.cout, scale, shift, u.amax, u.bound)
+        self._fwd_bn_act(u, training, scale, shift)
+
+    def _fwd_bn_act_pool(self, u, scale, shift):
+        """BatchNorm apply + activation + the 2x2 pool behind it + the pooled tensor's planes in one launch; the
+        unpooled activation is not written (its only reader would have been the pool)"""
+        pu = u.pool_fuse
+        ppl = self._xplanes.get(pu.out.tid) if pu.out.c % 16 == 0 else None
+        ops.bn_act_maxpool2x2_fwd(u.y, u.cout, scale, shift, u.act, pu.argmax,
+                                  out=pu.buf if (pu.f32_needed or ppl is None) else None, planes=ppl,
+                                  bn_bound=u.bound, out_bound=self._tb[pu.out.tid])
+        self._tbound_set.add(pu.out.tid)
+        if ppl is not None:
+            self._xp_valid.add(pu.out.tid)
+        pu.fused_this_pass = True
+
+    def _fwd_bn_act(self, u, training, scale, shift):
+        """BatchNorm apply + activation (+ residual Add) of a conv + BN unit, and the planes of its result"""
+        res = self.act[u.residual.tid] if u.residual is not None else None
+        res_pl = None
+        if (res is not None and training and self._res_from_planes and u.cout % 16 == 0
+                and u.residual.tid in self._xp_valid and u.residual.tid in self._tbound_set):
+            res_pl, res = self._xplanes[u.residual.tid], None   # (its fp32 copy may not have been written)
+        # consumers that are planes-capable convs get their operand straight from this kernel; the scale
+        # comes from the bound bn_finalize (training) / bn_infer_bound (inference) derived from the conv
+        # epilogue's per-channel max|y|
+        pl = self._xplanes.get(u.out.tid) if u.cout % 16 == 0 else None
+        if u.residual is not None and u.residual.tid not in self._tbound_set:
+            pl = None   # residual without a recorded bound: split its consumers' operand separately
+        else:
+            self._tbound_set.add(u.out.tid)
+        ops.bn_act_fwd(u.y, u.cout, scale, shift, u.act, res, out=u.a, planes=pl,
+                       want_out=not (training and pl is not None and not u.a_needed), bn_bound=u.bound,
+                       residual_bound=self._tb_float(u.residual.tid) if res is not None else None,
+                       out_bound=self._tb[u.out.tid], residual_planes=res_pl)
+        if pl is not None:
+            self._xp_valid.add(u.out.tid)
+
+    def _fwd_head(self, u, training):
+        bias, anchors = self.params.view(u.p_bias.name), self._anchors_dev.get(u.name)
+        if not training and self._infer_small_fuse and self._fuse_infer and u.planes_fwd:
+            ops.conv2d_fwd_head_unit(u.desc, self._xp(u.src), u.wp, bias, u.A, u.C, u.version, anchors, u.t, u.yact)
+            return
+        self._conv_fwd(u, bias, u.t)
+        ops.head_act_fwd(u.t, u.A, u.C, u.version, anchors, out=u.yact)
+
+    def _fwd_upsample(self, u, training):
+        if not training and self._infer_small_fuse and self._concat_planes and u.out.tid in self._up_producer:
+            u.concat_reads_through = True   # (the Concatenate behind it reads the half-size tensor itself)
+            return
+        ops.upsample2x_fwd(self.act[u.src.tid], u.buf, u.out.c, 0)
+
+    def _fwd_concat(self, u, training):
+        pl = self._xplanes.get(u.out.tid) if self._concat_planes else None
+        slots = [self._bound_alias.get(s.tid, s.tid) for s in u.srcs]
+        ups = [self._up_producer.get(s.tid) for s in u.srcs]
+        ups = [p if (p is not None and p.concat_reads_through) else None for p in ups]
+        for p in ups:
+            if p is not None:
+                p.concat_reads_through = False
+        rows, chans = self.batch * u.out.h * u.out.w, [s.c for s in u.srcs]
+        dst32 = u.buf if u.f32_needed else None
+        if (pl is not None and len(u.srcs) <= 4 and all(sl in self._tbound_set for sl in slots)
+                and all(s.c % 8 == 0 for s in u.srcs)):
+            if any(p is not None for p in ups):
+                ops.split_planes_concat_ex([self.act[p.src.tid] if p is not None else self.act[s.tid]
+                                            for s, p in zip(u.srcs, ups)], chans, [self._tb_words(sl) for sl in slots],
+                                           rows, pl, upsample=[p is not None for p in ups], hw=(u.out.h, u.out.w),
+                                           dst32=dst32, out_bound=self._tb[u.out.tid])
+            else:
+                ops.split_planes_concat([self.act[s.tid] for s in u.srcs], chans, [self._tb_float(sl) for sl in slots],
+                                        rows, pl, dst32=dst32, out_bound=self._tb[u.out.tid])
+            self._xp_valid.add(u.out.tid)
+            self._tbound_set.add(u.out.tid)
+            return
+        for p in ups:   # (this Concatenate cannot read through after all: make the upsampled tensors now)
+            if p is not None:
+                ops.upsample2x_fwd(self.act[p.src.tid], p.buf, p.out.c, 0)
+        off = 0
+        for s in u.srcs:
+            ops.copy_channels_in(self.act[s.tid], s.c, u.buf, u.out.c, off)
+            off += s.c
+
+    def _fwd_maxpool(self, u, training):
+        if getattr(u, "fused_this_pass", False):   # made by its producer's BatchNorm launch (pool_fuse)
+            u.fused_this_pass = False
+            return
+        ops.maxpool_fwd(self.act[u.src.tid], u.k, u.stride, u.pad_t, u.pad_l, u.out.h, u.out.w, u.buf,
+                        u.out.c, 0, u.argmax if training else None)
+
+    def _fwd_space_to_depth(self, u, training):
+        ops.space_to_depth2_fwd(self.act[u.src.tid], u.buf, u.out.c, 0)
+
+    def _stem_infer_unit(self, u, bias, scale, shift):
         """The RGB stem's inference unit in one launch (yolo_stem_fwd_infer_unit): direct fp32 convolution, folded
         BatchNormalization + activation in registers, the planes of the next convolution written by the same kernel; the image's
         max|x| comes from yolo_absmax_words. Returns False for any other unit."""
         pl = self._xplanes.get(u.out.tid)
         if u.residual is not None or pl is None or u.src.tid != self.input.tid or not ops.stem_infer_supported(u.desc):
             return False
-        if not self._infer_scale_valid:
-            ops.bn_fold_inference(u.cout, gamma, beta, self.state.view(u.s_mean.name), self.state.view(u.s_var.name),
-                                  scale, shift)
+        xin, w = self.act[u.src.tid], self.params.view(u.p_kernel.name)
+        if self._fold_infer_scale(u, scale, shift):
             if getattr(u, "stem_wt", None) is None:
                 u.stem_wt = torch.empty(28 * 32, device=self.device, dtype=torch.float32)
             ops.stem_filter_prep(w, bias, u.stem_wt)
-            pred = self._pred[u.pred_off:u.pred_off + 2]
-            ops.zero_bytes(pred)
-            ops.conv_pred_bound(w, u.cout, 27, scale, shift, bias, pred)
-        epi = {ACT_LEAKY: ops.EPI_AFFINE_LEAKY, ACT_MISH: ops.EPI_AFFINE_MISH}.get(u.act, ops.EPI_AFFINE)
+            ops.zero_bytes(u.pred)
+            ops.conv_pred_bound(w, u.cout, 27, scale, shift, bias, u.pred)
         row = self._tb_row(self.input.tid)
         n_in = ops.absmax_words(xin, row)
-        nw = ops.stem_fwd_infer_unit(u.desc, xin, u.stem_wt, epi, scale, shift, self._pred[u.pred_off:u.pred_off + 2], row[:n_in],
+        nw = ops.stem_fwd_infer_unit(u.desc, xin, u.stem_wt, _epilogue(u), scale, shift, u.pred, row[:n_in],
                                      u.a if u.a_needed else None, pl, self._tb_row(u.out.tid))
         self._tword_n[u.out.tid] = nw
         self._tbound_set.add(u.out.tid)
         self._xp_valid.add(u.out.tid)
         return True
 
-    def _fused_infer_unit(self, u, bias, gamma, beta, scale, shift):
+    def _fused_infer_unit(self, u, bias, scale, shift):
         """Inference form of a conv-BN-activation(-Add) unit in two launches (include/yolo_hip.h, fused epilogue): the
         folded BatchNormalization, the activation and the residual Add run in the conv's epilogue, then ONE pass turns
         the result into the planes of the consumer convolutions (bound = the epilogue's per-channel max + the
@@ -1058,24 +841,18 @@ class Network:
                                                                      dtype=torch.uint8)
         if pl is None or (u.residual is not None and u.residual.tid not in self._tbound_set):
             return False
-        if not self._infer_scale_valid:
-            ops.bn_fold_inference(u.cout, gamma, beta, self.state.view(u.s_mean.name), self.state.view(u.s_var.name),
-                                  scale, shift)
-        amax = self._aux[u.aux_off + AUX_WORDS:u.aux_off + AUX_WORDS + u.cout]
+        self._fold_infer_scale(u, scale, shift)
         res = self.act[u.residual.tid] if u.residual is not None else None
-        epi = {ACT_LEAKY: ops.EPI_AFFINE_LEAKY, ACT_MISH: ops.EPI_AFFINE_MISH}.get(u.act, ops.EPI_AFFINE)
-        tb = self._tbound
         src_slot = self._bound_alias.get(u.src.tid, u.src.tid)
         if self._infer_onepass and src_slot in self._tbound_set:
             # one pass: the kernel that finishes the tile writes the planes too, scaled by an a-priori bound
-            pred = self._pred[u.pred_off:u.pred_off + 2]
             if not self._infer_scale_valid:
-                ops.zero_bytes(pred)
-                ops.conv_pred_bound(self.params.view(u.p_kernel.name), u.cout, u.k * u.k * u.src.c, scale, shift, bias, pred)
-            nw = ops.conv2d_fwd_infer_unit(u.desc, self._xp(u.src), self._wplanes[u.wp_off:u.wp_off + u.wp_bytes], bias,
-                                           epi, scale, shift, res, u.a, amax, pred, self._tb_words(src_slot),
+                ops.zero_bytes(u.pred)
+                ops.conv_pred_bound(self.params.view(u.p_kernel.name), u.cout, u.k * u.k * u.src.c, scale, shift, bias, u.pred)
+            nw = ops.conv2d_fwd_infer_unit(u.desc, self._xp(u.src), u.wp, bias, _epilogue(u), scale, shift, res, u.a, u.amax,
+                                           u.pred, self._tb_words(src_slot),
                                            self._tb_words(u.residual.tid) if u.residual is not None else None, pl,
-                                           self._tb_row(u.out.tid), tb[u.out.tid:u.out.tid + 1])
+                                           self._tb_row(u.out.tid), self._tb[u.out.tid])
             if nw:
                 self._tword_n[u.out.tid] = nw
             self._tbound_set.add(u.out.tid)
@@ -1084,25 +861,25 @@ class Network:
             return True
         if not own_planes:
             return False
-        ops.conv2d_fwd_planes_epi(u.desc, self._xp(u.src), self._wplanes[u.wp_off:u.wp_off + u.wp_bytes], bias, epi, scale,
-                                  shift, residual=res, out=u.a, absmax=amax)
-        ops.split_planes_absmax(u.a, self.batch * u.out.h * u.out.w, u.cout, amax, pl,
+        ops.conv2d_fwd_planes_epi(u.desc, self._xp(u.src), u.wp, bias, _epilogue(u), scale, shift, residual=res, out=u.a,
+                                  absmax=u.amax)
+        ops.split_planes_absmax(u.a, self.batch * u.out.h * u.out.w, u.cout, u.amax, pl,
                                 extra_bound=self._tb_float(u.residual.tid) if u.residual is not None else None,
-                                out_bound=tb[u.out.tid:u.out.tid + 1])
+                                out_bound=self._tb[u.out.tid])
         self._tbound_set.add(u.out.tid)
         self._xp_valid.add(u.out.tid)
         return True
 
     # ---- backward -----------------------------------------------------------------------
+    def _stem_fused_bwd(self, u):
+        """the stem: BN / activation backward apply + filter gradient in one pass, no 32-channel dy tensor"""
+        return (self._stem_fused and not (u.planes_wgrad or u.planes_dgrad) and not self._needs_grad[u.src.tid]
+                and ops.stem_bn_bwd_supported(u.desc))
+
     def _takes_grad_slice(self, u):
         """can unit u's backward read dL/d(out) as a channel slice of a wider tensor? conv + BatchNormalization units without a
         residual Add (bn_act_bwd reads dout twice and nothing else does), not the fused stem path"""
-        if u.kind != "conv" or not u.bn or u.residual is not None or u.cout % 8 != 0:
-            return False
-        need_pl = u.planes_wgrad or u.planes_dgrad
-        if self._stem_fused and not need_pl and not self._needs_grad[u.src.tid] and ops.stem_bn_bwd_supported(u.desc):
-            return False
-        return True
+        return u.kind == "conv" and u.bn and u.residual is None and u.cout % 8 == 0 and not self._stem_fused_bwd(u)
 
     def _add_grad(self, grads, t, buf):
         """Contribute `buf` (same shape as tensor t) to dL/dt: alias if first, else add in place."""
@@ -1114,25 +891,14 @@ class Network:
         else:
             ops.axpy(cur, buf)
 
-    def _refresh_wT(self):
-        if self._wT_valid:
-            return
-        if self._jobs_wT is None:
-            self._jobs_wT = ops.BatchJobs("transpose", self.device)
-            for u in self.units:
-                if u.kind == "head" and u.cpad:
-                    self._jobs_wT.add_transpose(u.w_pad, u.wT_pad, u.cpad, 1, u.src.c)
-                elif u.kind in ("conv", "head"):
-                    cout = u.cout if u.kind == "conv" else u.out.c
-                    taps = u.k * u.k if u.kind == "conv" else 1
-                    n = cout * taps * u.src.c
-                    self._jobs_wT.add_transpose(self.params.view(u.p_kernel.name), self._wT[u.wT_off:u.wT_off + n],
-                                                cout, taps, u.src.c)
-        for u in self.units:
-            if u.kind == "head" and u.cpad:
-                tape.torch_op(lambda u=u: u.w_pad[:u.out.c * u.src.c].copy_(self.params.view(u.p_kernel.name).reshape(-1)))
-        self._jobs_wT.run()
-        self._wT_valid = True
+    def _grad_into(self, grads, t):
+        """(the gradient buffer of source tensor t, whether to accumulate into it): what an earlier contributor left, or a
+        new buffer, not initialised, that becomes dL/dt"""
+        cur = grads.get(t.tid)
+        if cur is not None:
+            return cur, True
+        cur = grads[t.tid] = torch.empty((self.batch, t.h, t.w, t.c), device=self.device, dtype=torch.float32)
+        return cur, False
 
     def _gview(self, spec):
         return self.grads[spec.offset:spec.offset + spec.size]
@@ -1152,147 +918,120 @@ class Network:
         for u in self.units:
             if getattr(u, "bnred", None) is not None:
                 u.bnred_done = False
-        grads = {}
-        for t, g in zip(self.outputs, douts):
-            grads[t.tid] = g
-        N = self.batch
+        grads = {t.tid: g for t, g in zip(self.outputs, douts)}
         for u in reversed(self.units):
             dout = grads.pop(u.out.tid, None)
             if dout is None:
                 continue  # output unused by the loss
             if isinstance(dout, ops.ChannelSlice) and not self._takes_grad_slice(u):
-                dout = dout.dense((N, u.out.h, u.out.w, u.out.c))
-            if u.kind == "conv":
-                xin = self.act[u.src.tid]
-                if u.bn:
-                    scale, shift, smean, sinv, _, red = self._bn_bufs(u)
-                    if u.residual is not None:
-                        self._add_grad(grads, u.residual, dout)
-                    # the gradient of the conv output goes straight into the planes the filter / data gradient
-                    # kernels read; the fp32 copy is written only if an fp32-path kernel still needs it
-                    need_pl = u.planes_wgrad or u.planes_dgrad
-                    # (a conv bias in front of BatchNormalization has the exact gradient 0 -- it cancels in y - mean -- so
-                    # nothing is computed for it: its slice of `grads` stays zero and no fp32 dy is needed on its account)
-                    need_f32 = (not u.planes_wgrad) or (self._needs_grad[u.src.tid] and not u.planes_dgrad)
-                    if (self._stem_fused and not need_pl and not self._needs_grad[u.src.tid]
-                            and ops.stem_bn_bwd_supported(u.desc)):
-                        # the stem: BN / activation backward apply + filter gradient in one pass, no 32-channel dy tensor
-                        ops.stem_bn_bwd_wgrad(u.desc, xin, u.y, dout, scale, shift, smean, sinv, u.act, red,
-                                              self._gview(u.p_gamma), self._gview(u.p_beta), self._gview(u.p_kernel),
-                                              fused=self._take_fused(u, dout))
-                        if self.grad_ready_hook is not None:
-                            tape.host_call(lambda u=u: self.grad_ready_hook(u))
-                        continue
-                    dyp = self._next_dyp_buffer(u) if need_pl else None
-                    dy = ops.bn_act_bwd(u.y, dout, u.cout, self.params.view(u.p_gamma.name), scale, shift, smean,
-                                        sinv, u.act, red, self._gview(u.p_gamma), self._gview(u.p_beta),
-                                        planes=dyp, want_dx=need_f32,
-                                        bound_aux=self._aux[u.aux_off + 1:u.aux_off + 69], fused=self._take_fused(u, dout),
-                                        tickets=(self._aux[u.aux_off + 69:u.aux_off + 69 + ops.BN_FOLD_TICKET_WORDS]
-                                                 if self._bn_fold else None))
-                else:
-                    dy = ops.act_bwd(u.y, dout, u.act) if u.act != ACT_LINEAR else dout
-                    dyp = self._dyp(u, dy)
-                dbias = self._gview(u.p_bias) if (u.p_bias is not None and not u.bn) else None
-                with self._beside_backward(dy):
-                    if u.planes_wgrad:
-                        ops.conv2d_wgrad_planes(u.desc, self._xplanes[u.src.tid], dyp, self._gview(u.p_kernel), dy=dy,
-                                                dbias=dbias)
-                    else:
-                        ops.conv2d_wgrad(u.desc, xin, dy, self._gview(u.p_kernel), dbias)
-                self._dgrad(grads, u, dy, u.cout * u.k * u.k * u.src.c, dyp)
-            elif u.kind == "head":
-                xin = self.act[u.src.tid]
-                dt = ops.head_act_bwd(u.yact, dout, u.A, u.C, u.version, self._anchors_dev.get(u.name),
-                                      danchors=self._anchor_grad_views.get(u.name) if self.anchors_trainable else None)
-                if u.cpad:
-                    rows = N * u.out.h * u.out.w
-                    dtp = ops.split_planes_padded(dt, rows, u.out.c, out=self._next_dyp_buffer(u))
-                    with self._beside_backward(dt):
-                        ops.zero_bytes(u.dw_pad)
-                        ops.conv2d_wgrad_planes(u.desc_pad, self._xplanes[u.src.tid], dtp, u.dw_pad)
-                        ops.axpy(self._gview(u.p_kernel), u.dw_pad[:u.out.c * u.src.c])
-                        ops.conv2d_wgrad_bias(dt, rows, u.out.c, self._gview(u.p_bias))
-                    if self._needs_grad[u.src.tid]:
-                        wTp = self._wplanes[u.wTp_pad_off:u.wTp_pad_off + u.wTp_pad_bytes]
-                        cur = grads.get(u.src.tid)
-                        b = self._bnred_of(u, cur)
-                        if cur is None:
-                            grads[u.src.tid] = ops.conv2d_dgrad_planes(u.desc_pad, dtp, wTp, bnred=b)
-                        else:
-                            ops.conv2d_dgrad_planes(u.desc_pad, dtp, wTp, dx=cur, accumulate=True, bnred=b)
-                    if self.grad_ready_hook is not None:
-                        tape.host_call(lambda u=u: self.grad_ready_hook(u))
-                    continue
-                dtp = self._dyp(u, dt)
-                with self._beside_backward(dt):
-                    if u.planes_wgrad:
-                        ops.conv2d_wgrad_planes(u.desc, self._xplanes[u.src.tid], dtp, self._gview(u.p_kernel), dy=dt,
-                                                dbias=self._gview(u.p_bias))
-                    else:
-                        ops.conv2d_wgrad(u.desc, xin, dt, self._gview(u.p_kernel), self._gview(u.p_bias))
-                self._dgrad(grads, u, dt, u.out.c * u.src.c, dtp)
-            elif u.kind == "upsample":
-                if self._needs_grad[u.src.tid]:
-                    cur = grads.get(u.src.tid)
-                    if cur is None:
-                        cur = torch.empty((N, u.src.h, u.src.w, u.src.c), device=self.device, dtype=torch.float32)
-                        ops.upsample2x_bwd(dout, u.out.c, 0, cur, accumulate=False)
-                        grads[u.src.tid] = cur
-                    else:
-                        ops.upsample2x_bwd(dout, u.out.c, 0, cur, accumulate=True)
-            elif u.kind == "concat":
-                off = 0
-                for s in u.srcs:
-                    if self._needs_grad[s.tid]:
-                        cur = grads.get(s.tid)
-                        if (cur is None and self._concat_grad_slices and self._n_consumers.get(s.tid, 0) == 1
-                                and s.producer is not None and self._takes_grad_slice(s.producer)
-                                and s.c % 8 == 0 and off % 4 == 0 and u.out.c % 4 == 0):
-                            grads[s.tid] = ops.ChannelSlice(dout, u.out.c, off, s.c)   # read in place by bn_act_bwd
-                            off += s.c
-                            continue
-                        if cur is None:
-                            cur = torch.empty((N, s.h, s.w, s.c), device=self.device, dtype=torch.float32)
-                            ops.copy_channels_out(dout, u.out.c, off, cur, s.c, accumulate=False)
-                            grads[s.tid] = cur
-                        else:
-                            ops.copy_channels_out(dout, u.out.c, off, cur, s.c, accumulate=True)
-                    off += s.c
-            elif u.kind == "maxpool":
-                if self._needs_grad[u.src.tid]:
-                    cur = grads.get(u.src.tid)
-                    if (u.k == 2 and u.stride == 2 and u.pad_t == 0 and u.pad_l == 0 and u.src.h == 2 * u.out.h
-                            and u.src.w == 2 * u.out.w and u.out.c % 4 == 0 and torch.is_tensor(dout) and dout.is_contiguous()
-                            and (cur is None or torch.is_tensor(cur))):
-                        # the windows tile the input: every input position is written / added to once, no zero fill, no atomics
-                        if cur is None:
-                            cur = torch.empty((N, u.src.h, u.src.w, u.src.c), device=self.device, dtype=torch.float32)
-                            grads[u.src.tid] = cur
-                            ops.maxpool2x2_bwd(dout, N, u.out.h, u.out.w, u.out.c, u.argmax, cur, False)
-                        else:
-                            ops.maxpool2x2_bwd(dout, N, u.out.h, u.out.w, u.out.c, u.argmax, cur, True)
-                        continue
-                    if cur is None:
-                        cur = torch.empty((N, u.src.h, u.src.w, u.src.c), device=self.device, dtype=torch.float32)
-                        ops.zero_bytes(cur)
-                        grads[u.src.tid] = cur
-                    if u.stride == 1 and (u.out.h, u.out.w) == (u.src.h, u.src.w):
-                        ops.maxpool_bwd_same(dout, N, u.out.h, u.out.w, u.out.c, u.out.c, 0, u.argmax, u.k, u.pad_t, u.pad_l, cur)
-                    else:
-                        ops.maxpool_bwd(dout, N, u.out.h, u.out.w, u.out.c, u.out.c, 0, u.argmax, cur)
-            elif u.kind == "space_to_depth":
-                if self._needs_grad[u.src.tid]:
-                    cur = grads.get(u.src.tid)
-                    if cur is None:
-                        cur = torch.empty((N, u.src.h, u.src.w, u.src.c), device=self.device, dtype=torch.float32)
-                        ops.space_to_depth2_bwd(dout, u.out.c, 0, cur, accumulate=False)
-                        grads[u.src.tid] = cur
-                    else:
-                        ops.space_to_depth2_bwd(dout, u.out.c, 0, cur, accumulate=True)
-            if self.grad_ready_hook is not None and u.kind in ("conv", "head"):
+                dout = dout.dense((self.batch, u.out.h, u.out.w, u.out.c))
+            getattr(self, "_bwd_" + u.kind)(u, dout, grads)
+            if self.grad_ready_hook is not None and has_filter(u):
                 tape.host_call(lambda u=u: self.grad_ready_hook(u))
         self._join_wgrad()
+
+    def _bwd_conv(self, u, dout, grads):
+        if u.bn:
+            scale, shift, smean, sinv, _, red = self._bn_bufs(u)
+            if u.residual is not None:
+                self._add_grad(grads, u.residual, dout)
+            if self._stem_fused_bwd(u):
+                ops.stem_bn_bwd_wgrad(u.desc, self.act[u.src.tid], u.y, dout, scale, shift, smean, sinv, u.act, red,
+                                      self._gview(u.p_gamma), self._gview(u.p_beta), self._gview(u.p_kernel),
+                                      fused=self._take_fused(u, dout))
+                return
+            # the gradient of the conv output goes straight into the planes the filter / data gradient
+            # kernels read; the fp32 copy is written only if an fp32-path kernel still needs it
+            # (a conv bias in front of BatchNormalization has the exact gradient 0 -- it cancels in y - mean -- so
+            # nothing is computed for it: its slice of `grads` stays zero and no fp32 dy is needed on its account)
+            need_f32 = (not u.planes_wgrad) or (self._needs_grad[u.src.tid] and not u.planes_dgrad)
+            dyp = self._next_dyp_buffer(u) if (u.planes_wgrad or u.planes_dgrad) else None
+            dy = ops.bn_act_bwd(u.y, dout, u.cout, self.params.view(u.p_gamma.name), scale, shift, smean,
+                                sinv, u.act, red, self._gview(u.p_gamma), self._gview(u.p_beta),
+                                planes=dyp, want_dx=need_f32, bound_aux=u.red_bound, fused=self._take_fused(u, dout),
+                                tickets=u.tickets if self._bn_fold else None)
+        else:
+            dy = ops.act_bwd(u.y, dout, u.act) if u.act != ACT_LINEAR else dout
+            dyp = self._dyp(u, dy)
+        dbias = self._gview(u.p_bias) if (u.p_bias is not None and not u.bn) else None
+        self._filter_and_data_grad(u, dy, dyp, dbias, grads)
+
+    def _bwd_head(self, u, dout, grads):
+        dt = ops.head_act_bwd(u.yact, dout, u.A, u.C, u.version, self._anchors_dev.get(u.name),
+                              danchors=self._anchor_grad_views.get(u.name) if self.anchors_trainable else None)
+        if not u.cpad:
+            return self._filter_and_data_grad(u, dt, self._dyp(u, dt), self._gview(u.p_bias), grads)
+        rows = self.batch * u.out.h * u.out.w
+        dtp = ops.split_planes_padded(dt, rows, u.out.c, out=self._next_dyp_buffer(u))
+        with self._beside_backward(dt):
+            ops.zero_bytes(u.dw_pad)
+            ops.conv2d_wgrad_planes(u.desc_pad, self._xplanes[u.src.tid], dtp, u.dw_pad)
+            ops.axpy(self._gview(u.p_kernel), u.dw_pad[:u.out.c * u.src.c])
+            ops.conv2d_wgrad_bias(dt, rows, u.out.c, self._gview(u.p_bias))
+        if self._needs_grad[u.src.tid]:
+            had = grads.get(u.src.tid)
+            b = self._bnred_of(u, had)
+            cur, acc = self._grad_into(grads, u.src)
+            ops.conv2d_dgrad_planes(u.desc_pad, dtp, u.wTp_pad, dx=cur, accumulate=acc, bnred=b)
+
+    def _filter_and_data_grad(self, u, dy, dyp, dbias, grads):
+        """filter gradient of a conv / head unit beside the main stream, then its data gradient"""
+        with self._beside_backward(dy):
+            if u.planes_wgrad:
+                ops.conv2d_wgrad_planes(u.desc, self._xplanes[u.src.tid], dyp, self._gview(u.p_kernel), dy=dy, dbias=dbias)
+            else:
+                ops.conv2d_wgrad(u.desc, self.act[u.src.tid], dy, self._gview(u.p_kernel), dbias)
+        if not self._needs_grad[u.src.tid]:
+            return
+        b = self._bnred_of(u, grads.get(u.src.tid)) if u.planes_dgrad else None
+        cur, acc = self._grad_into(grads, u.src)
+        if u.planes_dgrad:
+            ops.conv2d_dgrad_planes(u.desc, dyp, u.wTp, dx=cur, accumulate=acc, bnred=b)
+        else:
+            ops.conv2d_dgrad(u.desc, dy, u.wT, dx=cur, accumulate=acc)
+
+    def _bwd_upsample(self, u, dout, grads):
+        if self._needs_grad[u.src.tid]:
+            cur, acc = self._grad_into(grads, u.src)
+            ops.upsample2x_bwd(dout, u.out.c, 0, cur, accumulate=acc)
+
+    def _bwd_concat(self, u, dout, grads):
+        off = 0
+        for s in u.srcs:
+            if not self._needs_grad[s.tid]:
+                pass
+            elif (s.tid not in grads and self._concat_grad_slices and self._n_consumers.get(s.tid, 0) == 1
+                    and s.producer is not None and self._takes_grad_slice(s.producer)
+                    and s.c % 8 == 0 and off % 4 == 0 and u.out.c % 4 == 0):
+                grads[s.tid] = ops.ChannelSlice(dout, u.out.c, off, s.c)   # read in place by bn_act_bwd
+            else:
+                cur, acc = self._grad_into(grads, s)
+                ops.copy_channels_out(dout, u.out.c, off, cur, s.c, accumulate=acc)
+            off += s.c
+
+    def _bwd_maxpool(self, u, dout, grads):
+        if not self._needs_grad[u.src.tid]:
+            return
+        N, had = self.batch, grads.get(u.src.tid)
+        tiles = (u.k == 2 and u.stride == 2 and u.pad_t == 0 and u.pad_l == 0 and u.src.h == 2 * u.out.h
+                 and u.src.w == 2 * u.out.w and u.out.c % 4 == 0 and torch.is_tensor(dout) and dout.is_contiguous()
+                 and (had is None or torch.is_tensor(had)))
+        cur, acc = self._grad_into(grads, u.src)
+        if tiles:
+            # the windows tile the input: every input position is written / added to once, no zero fill, no atomics
+            ops.maxpool2x2_bwd(dout, N, u.out.h, u.out.w, u.out.c, u.argmax, cur, acc)
+            return
+        if not acc:
+            ops.zero_bytes(cur)
+        if u.stride == 1 and (u.out.h, u.out.w) == (u.src.h, u.src.w):
+            ops.maxpool_bwd_same(dout, N, u.out.h, u.out.w, u.out.c, u.out.c, 0, u.argmax, u.k, u.pad_t, u.pad_l, cur)
+        else:
+            ops.maxpool_bwd(dout, N, u.out.h, u.out.w, u.out.c, u.out.c, 0, u.argmax, cur)
+
+    def _bwd_space_to_depth(self, u, dout, grads):
+        if self._needs_grad[u.src.tid]:
+            cur, acc = self._grad_into(grads, u.src)
+            ops.space_to_depth2_bwd(dout, u.out.c, 0, cur, accumulate=acc)
 
     # The filter gradient of a layer is independent of everything the backward pass does next (its data
     # gradient, the BatchNorm backward of the layer below, ...): it is enqueued on a second stream so that it
@@ -1345,8 +1084,7 @@ class Network:
         """planes of this layer's dy (one scratch, consumed by the filter and data gradients right away)"""
         if not (u.planes_wgrad or u.planes_dgrad):
             return None
-        cout = u.cout if u.kind == "conv" else u.out.c
-        return ops.split_planes(dy, self.batch * u.out.h * u.out.w, cout, out=self._next_dyp_buffer(u))
+        return ops.split_planes(dy, self.batch * u.out.h * u.out.w, u.cout, out=self._next_dyp_buffer(u))
 
     def _bnred_of(self, w, cur):
         """the fused reduction this writer's data gradient makes (None: none). cur = the gradient it adds into, if any: a
@@ -1366,24 +1104,6 @@ class Network:
         if not torch.is_tensor(dout):
             raise YoloHipError(f"{u.name}: fused reduction made for a gradient that arrives as a channel slice")
         return b
-
-    def _dgrad(self, grads, u, dy, wsize, dyp=None):
-        if not self._needs_grad[u.src.tid]:
-            return
-        cur = grads.get(u.src.tid)
-        if u.planes_dgrad:
-            wTp = self._wplanes[u.wTp_off:u.wTp_off + u.wTp_bytes]
-            b = self._bnred_of(u, cur)
-            if cur is None:
-                grads[u.src.tid] = ops.conv2d_dgrad_planes(u.desc, dyp, wTp, bnred=b)
-            else:
-                ops.conv2d_dgrad_planes(u.desc, dyp, wTp, dx=cur, accumulate=True, bnred=b)
-            return
-        wT = self._wT[u.wT_off:u.wT_off + wsize]
-        if cur is None:
-            grads[u.src.tid] = ops.conv2d_dgrad(u.desc, dy, wT)
-        else:
-            ops.conv2d_dgrad(u.desc, dy, wT, dx=cur, accumulate=True)
 
     # ---- weights ------------------------------------------------------------------------
     def named_weights(self):
