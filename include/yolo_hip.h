@@ -254,6 +254,32 @@ int yolo_split_planes_concat_ex(const float* const* srcs_host, const int* channe
  * else is yolo_conv2d_fwd_planes + yolo_head_act_fwd behind this entry. t and y are both written. */
 int yolo_conv2d_fwd_head_unit(const yolo_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
                               int A, int C, int version, const float* anchors, float* t, float* y, void* stream);
+/* Half-precision INFERENCE: the four planes forward entry points above with one more argument, `precision`, in front of the
+ * stream. YOLO_PREC_F32 is the entry point without the suffix, bit for bit (those call these). YOLO_PREC_F16 issues ONE fp16
+ * MFMA pass (h*h) instead of three (l*h + h*l + h*h, csrc/planes.hpp): a third of the matrix work. Accuracy contract: the
+ * result is the float64 convolution of the ROUNDED operands hx = fp16(s_x x) / s_x and hw = fp16(s_w w) / s_w (s = the
+ * power-of-two scales in the planes' headers) up to fp32 accumulation -- within 2e-5 of max|y| of that convolution, the bar
+ * the three-pass kernels are held to against the unrounded one -- and therefore off the convolution of the unrounded
+ * operands by fp16 operand rounding (2^-11 relative per element): 2.6e-4 .. 4.5e-4 of max|y| for N(0,1) inputs and He-scaled
+ * filters, where YOLO_PREC_F32 stays below 2e-5. Operands that fp16 holds exactly after the scale give bit-identical results
+ * in both modes. Everything else is the same in both: tile choice and launches, epilogues, bounds and scales of the planes
+ * going out (both planes are written), the a-priori bound of yolo_conv_pred_bound. The precision is an argument, not a
+ * yolo_set_option key: two models in one process may want different ones. stats != NULL (the training forward) with
+ * YOLO_PREC_F16, and any other precision value, return YOLO_ERR_INVALID_ARG: training stays fp32-grade. */
+enum { YOLO_PREC_F32 = 0, YOLO_PREC_F16 = 1 };
+int yolo_conv2d_fwd_planes_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
+                              float* y, double* stats, unsigned* absmax, int precision, void* stream);
+int yolo_conv2d_fwd_planes_epi_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
+                                  int epilogue, const float* scale, const float* shift, const float* residual, float* y,
+                                  unsigned* absmax, int precision, void* stream);
+int yolo_conv2d_fwd_infer_unit_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
+                                  int epilogue, const float* scale, const float* shift, const float* residual, float* y,
+                                  unsigned* absmax, const float* pred2, const void* in_bound, int in_n,
+                                  const void* residual_bound, int residual_n, void* out_planes, unsigned* out_words,
+                                  float* out_bound, int* out_n_host, int precision, void* stream);
+int yolo_conv2d_fwd_head_unit_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes, const float* bias,
+                                 int A, int C, int version, const float* anchors, float* t, float* y, int precision,
+                                 void* stream);
 /* yolo_conv2d_wgrad on pre-split operands (dw += ..., same contract; the bias gradient stays with
  * yolo_conv2d_wgrad_bias on the fp32 dy). Requires Cin % 16 == 0, Cout % 16 == 0, Cout >= 32, kh*kw*Cin >= 64.
  * Two kernels behind it, same results to fp32 summation order: 3x3 stride-1 'same' layers with Cout % 128 == 0 and

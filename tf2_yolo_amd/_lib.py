@@ -15,6 +15,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libyolo_hip.so")
 
 ACT_LINEAR, ACT_LEAKY, ACT_MISH = 0, 1, 2
+PREC_F32, PREC_F16 = 0, 1   # YOLO_PREC_*: MFMA passes of the inference forward (three / one)
+_PRECISIONS = {"fp32": PREC_F32, "fp16": PREC_F16}
+
+
+def precision_enum(precision):
+    """'fp32' / 'fp16' -> YOLO_PREC_F32 / YOLO_PREC_F16; anything else is a ValueError"""
+    try:
+        return _PRECISIONS[precision]
+    except (KeyError, TypeError):
+        raise ValueError(f"precision must be 'fp32' or 'fp16', got {precision!r}") from None
 NMS_HARD, NMS_SOFT, NMS_DIOU = 1, 2, 3
 
 
@@ -76,6 +86,11 @@ SIGNATURES = {
     "yolo_split_planes_concat_ex": (c_int, [POINTER(c_void_p), POINTER(c_int), POINTER(c_void_p), POINTER(c_int), POINTER(c_int),
                                             c_int, c_int, c_int, _LL, _P, _P, _P, _P]),
     "yolo_conv2d_fwd_head_unit": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "yolo_conv2d_fwd_planes_ex": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, c_int, _P]),
+    "yolo_conv2d_fwd_planes_epi_ex": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P, _P, _P, _P, _P, c_int, _P]),
+    "yolo_conv2d_fwd_infer_unit_ex": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, _P, c_int,
+                                              _P, _P, _P, POINTER(c_int), c_int, _P]),
+    "yolo_conv2d_fwd_head_unit_ex": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_int, _P]),
     "yolo_conv2d_fwd_absmax": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "yolo_conv2d_dgrad_planes": (c_int, [POINTER(ConvDesc), _P, _P, _P, c_int, _P]),
     "yolo_conv2d_wgrad_planes": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P]),

@@ -901,10 +901,23 @@ extern "C" int yolo_conv2d_fwd(const yolo_conv_desc* d, const float* x, const fl
   return yolo_conv2d_fwd_absmax(d, x, w, bias, y, stats, nullptr, stream);
 }
 
+// precision of the *_ex forward entry points -> GatherConvArgs::one_pass; anything but the two enumerators is an error
+#define YOLO_REQUIRE_PRECISION(precision, what) \
+  YOLO_REQUIRE((precision) == YOLO_PREC_F32 || (precision) == YOLO_PREC_F16, what ": unknown precision %d", (precision))
+
 extern "C" int yolo_conv2d_fwd_planes(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
                                       const float* bias, float* y, double* stats, unsigned* absmax, void* stream) {
+  return yolo_conv2d_fwd_planes_ex(d, x_planes, w_planes, bias, y, stats, absmax, YOLO_PREC_F32, stream);
+}
+
+extern "C" int yolo_conv2d_fwd_planes_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
+                                         const float* bias, float* y, double* stats, unsigned* absmax, int precision,
+                                         void* stream) {
   if (int rc = validate_desc(d)) return rc;
   YOLO_REQUIRE(x_planes && w_planes && y, "conv_fwd_planes: null pointer");
+  YOLO_REQUIRE_PRECISION(precision, "conv_fwd_planes");
+  YOLO_REQUIRE(precision == YOLO_PREC_F32 || stats == nullptr,
+               "conv_fwd_planes: BatchNorm statistics (the training forward) are fp32-grade only");
   GatherConvArgs a{};
   a.src = reinterpret_cast<const float*>(x_planes);
   a.wgt = reinterpret_cast<const float*>(w_planes);
@@ -913,6 +926,7 @@ extern "C" int yolo_conv2d_fwd_planes(const yolo_conv_desc* d, const void* x_pla
   fill_fwd_args(d, a);
   a.stats = stats;
   a.absmax = absmax;
+  a.one_pass = precision == YOLO_PREC_F16;
   YOLO_REQUIRE(gather_planes_supported(a), "conv_fwd_planes: needs Cin %% 16 == 0 and Cout >= 32");
   return launch_gather_planes(a, as_stream(stream));
 }
@@ -922,8 +936,16 @@ extern "C" int yolo_conv2d_fwd_planes(const yolo_conv_desc* d, const void* x_pla
 extern "C" int yolo_conv2d_fwd_planes_epi(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
                                           const float* bias, int epilogue, const float* scale, const float* shift,
                                           const float* residual, float* y, unsigned* absmax, void* stream) {
+  return yolo_conv2d_fwd_planes_epi_ex(d, x_planes, w_planes, bias, epilogue, scale, shift, residual, y, absmax, YOLO_PREC_F32,
+                                       stream);
+}
+
+extern "C" int yolo_conv2d_fwd_planes_epi_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
+                                             const float* bias, int epilogue, const float* scale, const float* shift,
+                                             const float* residual, float* y, unsigned* absmax, int precision, void* stream) {
   if (int rc = validate_desc(d)) return rc;
   YOLO_REQUIRE(x_planes && w_planes && y, "conv_fwd_planes_epi: null pointer");
+  YOLO_REQUIRE_PRECISION(precision, "conv_fwd_planes_epi");
   YOLO_REQUIRE(epilogue == YOLO_EPI_NONE || epilogue == YOLO_EPI_AFFINE_LEAKY || epilogue == YOLO_EPI_AFFINE_MISH ||
                epilogue == YOLO_EPI_AFFINE, "conv_fwd_planes_epi: bad epilogue %d", epilogue);
   YOLO_REQUIRE(epilogue == YOLO_EPI_NONE || (scale && shift), "conv_fwd_planes_epi: affine epilogue without scale / shift");
@@ -941,6 +963,7 @@ extern "C" int yolo_conv2d_fwd_planes_epi(const yolo_conv_desc* d, const void* x
     a.epi_act = epilogue == YOLO_EPI_AFFINE_LEAKY ? YOLO_ACT_LEAKY : epilogue == YOLO_EPI_AFFINE_MISH ? YOLO_ACT_MISH : YOLO_ACT_LINEAR;
   }
   a.epi_res = residual;
+  a.one_pass = precision == YOLO_PREC_F16;
   YOLO_REQUIRE(gather_planes_supported(a), "conv_fwd_planes_epi: needs Cin %% 16 == 0 and Cout >= 32");
   return launch_gather_planes(a, as_stream(stream));
 }
@@ -959,7 +982,19 @@ extern "C" int yolo_conv2d_fwd_infer_unit(const yolo_conv_desc* d, const void* x
                                           const void* in_bound, int in_n, const void* residual_bound, int residual_n,
                                           void* out_planes, unsigned* out_words, float* out_bound, int* out_n_host,
                                           void* stream) {
+  return yolo_conv2d_fwd_infer_unit_ex(d, x_planes, w_planes, bias, epilogue, scale, shift, residual, y, absmax, pred, in_bound,
+                                       in_n, residual_bound, residual_n, out_planes, out_words, out_bound, out_n_host,
+                                       YOLO_PREC_F32, stream);
+}
+
+extern "C" int yolo_conv2d_fwd_infer_unit_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
+                                             const float* bias, int epilogue, const float* scale, const float* shift,
+                                             const float* residual, float* y, unsigned* absmax, const float* pred,
+                                             const void* in_bound, int in_n, const void* residual_bound, int residual_n,
+                                             void* out_planes, unsigned* out_words, float* out_bound, int* out_n_host,
+                                             int precision, void* stream) {
   if (int rc = validate_desc(d)) return rc;
+  YOLO_REQUIRE_PRECISION(precision, "conv_fwd_infer_unit");
   YOLO_REQUIRE(x_planes && w_planes && y && absmax && pred && in_bound && out_planes && out_words && out_bound && out_n_host,
                "conv_fwd_infer_unit: null pointer");
   YOLO_REQUIRE(epilogue == YOLO_EPI_AFFINE_LEAKY || epilogue == YOLO_EPI_AFFINE_MISH || epilogue == YOLO_EPI_AFFINE,
@@ -989,6 +1024,7 @@ extern "C" int yolo_conv2d_fwd_infer_unit(const yolo_conv_desc* d, const void* x
   a.pl_res_bound = residual != nullptr ? reinterpret_cast<const unsigned*>(residual_bound) : nullptr;
   a.pl_res_n = residual != nullptr ? residual_n : 0;
   a.pl_out_words = out_words;
+  a.one_pass = precision == YOLO_PREC_F16;
   YOLO_REQUIRE(gather_planes_supported(a), "conv_fwd_infer_unit: needs Cin %% 16 == 0 and Cout >= 32");
   // few output pixels (bs-1 predict): the whole unit in ONE launch, K split across the waves of a workgroup (conv_small.hip)
   if (conv_small_supported(a)) return launch_conv_small(a, as_stream(stream), out_n_host);
@@ -1089,7 +1125,14 @@ extern "C" int yolo_split_planes_concat_ex(const float* const* srcs_host, const 
 extern "C" int yolo_conv2d_fwd_head_unit(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
                                          const float* bias, int A, int C, int version, const float* anchors, float* t,
                                          float* y, void* stream) {
+  return yolo_conv2d_fwd_head_unit_ex(d, x_planes, w_planes, bias, A, C, version, anchors, t, y, YOLO_PREC_F32, stream);
+}
+
+extern "C" int yolo_conv2d_fwd_head_unit_ex(const yolo_conv_desc* d, const void* x_planes, const void* w_planes,
+                                            const float* bias, int A, int C, int version, const float* anchors, float* t,
+                                            float* y, int precision, void* stream) {
   if (int rc = validate_desc(d)) return rc;
+  YOLO_REQUIRE_PRECISION(precision, "conv_fwd_head_unit");
   YOLO_REQUIRE(x_planes && w_planes && t && y && A > 0 && C > 0, "conv_fwd_head_unit: bad args");
   YOLO_REQUIRE(d->Cout == A * (5 + C), "conv_fwd_head_unit: Cout = %d is not A (5 + C) = %d", d->Cout, A * (5 + C));
   GatherConvArgs a{};
@@ -1098,6 +1141,7 @@ extern "C" int yolo_conv2d_fwd_head_unit(const yolo_conv_desc* d, const void* x_
   a.bias = bias;
   a.dst = t;
   fill_fwd_args(d, a);
+  a.one_pass = precision == YOLO_PREC_F16;
   YOLO_REQUIRE(gather_planes_supported(a), "conv_fwd_head_unit: needs Cin %% 16 == 0 and Cout >= 32");
   if ((version == YOLO_HEAD_V3 || version == YOLO_HEAD_V4) && anchors != nullptr) {
     a.head_y = y;

@@ -43,6 +43,7 @@ struct GatherConvArgs {
   int vec_store; // planes kernels, 128x128 tiles: output through LDS as dwordx4 rows (YOLO_VEC_STORE, default 1)
   int kc;        // planes kernels: 16-channel blocks per chunk of the stage order
   int dbg;       // planes kernels: diagnostic knock-outs (YOLO_PLANES_DBG), 0 in production
+  int one_pass;  // planes kernels, inference forward only (YOLO_PREC_F16): the h*h MFMA pass alone; never changes the tile choice
   // fused inference epilogue of the planes kernels (planes_epilogue.hpp): dst = act(epi_scale[c] * y + epi_shift[c])
   // (+ epi_res, a tensor laid out like dst); epi_scale == nullptr: plain y. absmax then holds max|dst| before the residual
   const float* epi_scale;

@@ -287,8 +287,13 @@ constexpr int PF_MULTI = 64;     // the parity classes of a strided data gradien
 constexpr int PF_DEEP1 = 128;    // one more DMA stage in the ring
 constexpr int PF_DEEP2 = 256;    // two more
 constexpr int PF_BNRED = 512;    // the fused BatchNorm-backward reduction
-template <int BM, int BN, int WGM, int WGN, int FORM = 0>
+// PASSES: 3 = l*h + h*l + h*h (fp32-grade), 1 = h*h alone (planes.hpp, ONE PASS): the inference forward forms only
+// (plain and split-K). The DMA schedule, the LDS image and the vmcnt immediates are the same: both planes are fetched.
+template <int BM, int BN, int WGM, int WGN, int FORM = 0, int PASSES = 3>
 __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gather_conv_planes_kernel(const GatherConvArgs a) {
+  static_assert(planes_passes_ok(PASSES), "1 or 3 MFMA passes");
+  static_assert(PASSES == 3 || (FORM & (PF_MULTI | PF_BNRED)) == 0, "one pass: forward inference forms only");
+  constexpr int NPL = planes_frag_planes<PASSES>;   // planes read from LDS into fragments
   constexpr int NW = WGM * WGN;
   constexpr int TM = BM / WGM / 32;
   constexpr int TN = BN / WGN / 32;
@@ -439,12 +444,13 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
 
   // two fragment register sets: the MFMAs of stage kt run on one while stage kt+1 is read into the other
-  f16x8 fa[2][PL_PLANES][TM], fb[2][PL_PLANES][TN];
+  // (one pass: the l fragments do not exist -- half the ds_read_b128, 4 (TM + TN) fewer registers per set)
+  f16x8 fa[2][NPL][TM], fb[2][NPL][TN];
   auto read_frags = [&](int buf, auto SET) {
     constexpr int S = decltype(SET)::value;
     const unsigned char* sb = smem + buf * STAGE_BYTES + lane * 16;
 #pragma unroll
-    for (int p = 0; p < PL_PLANES; ++p) {
+    for (int p = 0; p < NPL; ++p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
         fa[S][p][i] = *reinterpret_cast<const f16x8*>(sb + ((wm * TM + i) * PL_PLANES + p) * 1024);
@@ -458,11 +464,12 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
   // on the MFMAs already queued.
   auto mfma_stage = [&](auto SET, int wbuf) {
     constexpr int S = decltype(SET)::value;
-    constexpr int NM = TM * TN * 3;
+    constexpr int NM = TM * TN * PASSES;
+    static_assert(dma_slots_cover(NM, ND), "every stage issues each of its ND DMAs exactly once, in order");
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int pa = (q == 0) ? 1 : 0;
-      const int pb = (q == 1) ? 1 : 0;
+    for (int q = 0; q < PASSES; ++q) {
+      const int pa = (PASSES == 3 && q == 0) ? 1 : 0;   // (one pass: h*h)
+      const int pb = (PASSES == 3 && q == 1) ? 1 : 0;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -471,7 +478,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, (WGM * WGN >= 4 ? 2 : 1)) void gath
           const int idx = (q * TM + i) * TN + j;
 #pragma unroll
           for (int d = 0; d < ND; ++d)
-            if (idx == (((d + 1) * NM) / (ND + 1) > 0 ? ((d + 1) * NM) / (ND + 1) - 1 : 0)) {
+            if (idx == dma_slot(d, NM, ND)) {
               __builtin_amdgcn_sched_barrier(0);
               if constexpr (!(FORM & 1)) issue_plane(d, wbuf);
               __builtin_amdgcn_sched_barrier(0);
@@ -563,6 +570,12 @@ static int launch_planes(GatherConvArgs& a, hipStream_t st) {
   a.bwd_nslots = (int)tiles_m;
   YOLO_BNRED_CHECK(a)
   constexpr auto plain = &gather_conv_planes_kernel<BM, BN, WGM, WGN, FORM>;   // (beside it: its split-K and BatchNorm-reduction forms)
+  // one MFMA pass (inference forward): the same tile, grid and split as three passes, another instantiation
+  constexpr bool HAS_ONE_PASS = (FORM & ~(PF_DEEP1 | PF_DEEP2)) == 0;
+  if (a.one_pass && (!HAS_ONE_PASS || a.stats != nullptr || a.bwd_y != nullptr || a.accumulate)) {
+    set_error("conv(planes): one MFMA pass is an inference-forward form only");
+    return YOLO_ERR_INVALID_ARG;
+  }
   a.split_parts = 1;
   if constexpr (BM == 128 && BN == 128 && WGM == 2 && WGN == 2 && FORM == 0) {
     // at least 8 stages per part (a.kc = the whole channel range in one chunk is the default stage order)
@@ -570,9 +583,11 @@ static int launch_planes(GatherConvArgs& a, hipStream_t st) {
     a.split_parts = conv_split_parts(a, nb, BM, min_cb, 4);
     if (a.split_parts > 1) {
       a.sk_slabs = conv_split_slabs();
-      if (int rc = launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, PF_SPLIT>, lds>(
-              dim3((unsigned)(nb * a.split_parts)), block, st, a, "gather_conv_planes_kernel(split)"))
-        return rc;
+      const int rc = a.one_pass ? launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, PF_SPLIT, 1>, lds>(
+                                      dim3((unsigned)(nb * a.split_parts)), block, st, a, "gather_conv_planes_kernel(split, one pass)")
+                                : launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, PF_SPLIT>, lds>(
+                                      dim3((unsigned)(nb * a.split_parts)), block, st, a, "gather_conv_planes_kernel(split)");
+      if (rc) return rc;
       return launch_split_reduce(a, BM, st);
     }
   }
@@ -583,6 +598,11 @@ static int launch_planes(GatherConvArgs& a, hipStream_t st) {
   } else if (a.bwd_y != nullptr) {
     set_error("conv(planes): this diagnostic instantiation has no fused BatchNorm-backward reduction");
     return YOLO_ERR_INVALID_ARG;
+  }
+  if constexpr (HAS_ONE_PASS) {
+    if (a.one_pass)
+      return launch_lds<gather_conv_planes_kernel<BM, BN, WGM, WGN, FORM, 1>, lds>(dim3((unsigned)nb), block, st, a,
+                                                                                  "gather_conv_planes_kernel(one pass)");
   }
   return launch_lds<plain, lds>(dim3((unsigned)nb), block, st, a, "gather_conv_planes_kernel");
 }

@@ -31,9 +31,14 @@ namespace yolo {
 
 constexpr int SM_WAVES = 8;   // waves per workgroup = K split
 
-template <int TM, int TN, int CH>
+// PASSES: 3 = al*bh + ah*bl + ah*bh, 1 = ah*bh alone (planes.hpp, ONE PASS): the l planes are neither requested nor held
+template <int TM, int TN, int CH, int PASSES = 3>
 struct SmallBuf {
   u32x4 ah[CH][TM], al[CH][TM], bh[CH][TN], bl[CH][TN];
+};
+template <int TM, int TN, int CH>
+struct SmallBuf<TM, TN, CH, 1> {
+  u32x4 ah[CH][TM], bh[CH][TN];
 };
 
 // NT taps (1 or 9); tile = 32 TM pixels x 32 TN filters (TM x TN accumulators per wave: an operand fragment a wave has
@@ -55,8 +60,9 @@ struct SmallLds {
   static constexpr int BYTES = MX + 3 * SM_WAVES * 4;
 };
 
-template <int NT, int TM, int TN, int CH, bool HEAD = false>
+template <int NT, int TM, int TN, int CH, bool HEAD = false, int PASSES = 3>
 __global__ __launch_bounds__(64 * SM_WAVES) void conv_small_kernel(const GatherConvArgs a) {
+  static_assert(planes_passes_ok(PASSES), "1 or 3 MFMA passes");
   constexpr int BMT = 32 * TM, BNT = 32 * TN, NB = TM * TN;
   constexpr int NTASK = (4 * NB + SM_WAVES - 1) / SM_WAVES;      // quarter-blocks per wave
   using LDS = SmallLds<TM, TN, NT>;
@@ -171,7 +177,7 @@ __global__ __launch_bounds__(64 * SM_WAVES) void conv_small_kernel(const GatherC
   const int nch = (per_wave + CH - 1) / CH;                      // chunks of CH steps
   // (t, kb) of the wave's next step, kept incrementally: the steps are requested in increasing order
   int nx_s = wave, nx_t = wave / KB, nx_kb = wave - (wave / KB) * KB;
-  using Buf = SmallBuf<TM, TN, CH>;
+  using Buf = SmallBuf<TM, TN, CH, PASSES>;
   auto load = [&](Buf& b) {
 #pragma unroll
     for (int u = 0; u < CH; ++u) {
@@ -185,13 +191,13 @@ __global__ __launch_bounds__(64 * SM_WAVES) void conv_small_kernel(const GatherC
           ao = s_aoff[live ? nx_t : 0][32 * i + r] + lane_unit + (live ? (unsigned)nx_kb * PL_RECORD : 0u);
         }
         b.ah[u][i] = *reinterpret_cast<const u32x4*>(srcp + ao);
-        b.al[u][i] = *reinterpret_cast<const u32x4*>(srcp + ao + 512);
+        if constexpr (PASSES == 3) b.al[u][i] = *reinterpret_cast<const u32x4*>(srcp + ao + 512);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const unsigned bo = live ? boff[j] + (unsigned)nx_s * PL_RECORD : bzero;
         b.bh[u][j] = *reinterpret_cast<const u32x4*>(wgtp + bo);
-        b.bl[u][j] = *reinterpret_cast<const u32x4*>(wgtp + bo + 512);
+        if constexpr (PASSES == 3) b.bl[u][j] = *reinterpret_cast<const u32x4*>(wgtp + bo + 512);
       }
       nx_s += SM_WAVES;
       nx_kb += SM_WAVES;
@@ -208,10 +214,12 @@ __global__ __launch_bounds__(64 * SM_WAVES) void conv_small_kernel(const GatherC
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          const f16x8 ah = __builtin_bit_cast(f16x8, b.ah[u][i]), al = __builtin_bit_cast(f16x8, b.al[u][i]);
-          const f16x8 bh = __builtin_bit_cast(f16x8, b.bh[u][j]), bl = __builtin_bit_cast(f16x8, b.bl[u][j]);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[i][j], 0, 0, 0);
+          const f16x8 ah = __builtin_bit_cast(f16x8, b.ah[u][i]), bh = __builtin_bit_cast(f16x8, b.bh[u][j]);
+          if constexpr (PASSES == 3) {
+            const f16x8 al = __builtin_bit_cast(f16x8, b.al[u][i]), bl = __builtin_bit_cast(f16x8, b.bl[u][j]);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[i][j], 0, 0, 0);
+          }
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[i][j], 0, 0, 0);
         }
   };
@@ -401,6 +409,9 @@ template <int NT, int TM, int TN, int CH, bool HEAD = false>
 static int launch_small(GatherConvArgs& a, hipStream_t st, int* nwg) {
   a.nblocks = (int)(((a.M + 32 * TM - 1) / (32 * TM)) * ((a.Cout + 32 * TN - 1) / (32 * TN)));
   *nwg = a.nblocks;
+  if (a.one_pass)   // (the same tile and grid: small_tile / small_head_tile never look at the precision)
+    return launch_lds<conv_small_kernel<NT, TM, TN, CH, HEAD, 1>, SmallLds<TM, TN, NT>::BYTES>(dim3((unsigned)a.nblocks), dim3(64 * SM_WAVES),
+                                                                                              st, a, "conv_small_kernel(one pass)");
   return launch_lds<conv_small_kernel<NT, TM, TN, CH, HEAD>, SmallLds<TM, TN, NT>::BYTES>(dim3((unsigned)a.nblocks), dim3(64 * SM_WAVES),
                                                                                          st, a, "conv_small_kernel");
 }

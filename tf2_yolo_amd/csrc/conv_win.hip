@@ -63,8 +63,14 @@ namespace yolo {
 // 64 pixels (104 / 208 in YOLOv3-416, 76 / 152 / 304 in YOLOv4-608).
 // WGN = 1: 64 filter columns per tile (BN = 64) with WGM = 4 waves of 64 x 64 stacked in M (256 output pixels = a
 // 16 x 16 patch): the Cout = 64 layers, which would waste half of a 128-column tile.
-template <int WGM, int NCH, bool STAMPS = false, bool SPLIT = false, bool SK = false, int WGN = 2, int GEO = 0, bool BNRED = false>
+// PASSES: 3 = l*h + h*l + h*h, 1 = h*h alone (planes.hpp, ONE PASS) -- the inference forward forms (plain, patch, split-K,
+// stream-K). Same DMA schedule, LDS image and vmcnt immediates: both planes of the window and of the filters are fetched.
+template <int WGM, int NCH, bool STAMPS = false, bool SPLIT = false, bool SK = false, int WGN = 2, int GEO = 0, bool BNRED = false,
+          int PASSES = 3>
 __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_win_kernel(const GatherConvArgs a) {
+  static_assert(planes_passes_ok(PASSES), "1 or 3 MFMA passes");
+  static_assert(PASSES == 3 || (!BNRED && !STAMPS), "one pass: forward inference forms only");
+  constexpr int NPL = planes_frag_planes<PASSES>;   // planes read from LDS into fragments
   constexpr int BM = 64 * WGM, BN = 64 * WGN;
   constexpr int NW = WGM * WGN;
   constexpr int TM = 2, TN = 2;
@@ -252,7 +258,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_win_kernel(const Gathe
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
 
-  f16x8 fa[2][PL_PLANES][TM], fb[2][PL_PLANES][TN];
+  f16x8 fa[2][NPL][TM], fb[2][NPL][TN];   // (one pass: no l fragments)
   // fragments of stage (cb, t) into register set S
   auto read_frags = [&](int cb, auto T, auto SET) {
     constexpr int S = decltype(SET)::value;
@@ -260,7 +266,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_win_kernel(const Gathe
     const unsigned so = (unsigned)((cb & 1) * WIN_BYTES + tapoff[t]);
     const unsigned char* sbB = smem + BRING + (t % 3) * BSTAGE + lane * 16;
 #pragma unroll
-    for (int p = 0; p < PL_PLANES; ++p) {
+    for (int p = 0; p < NPL; ++p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
         fa[S][p][i] = *reinterpret_cast<const f16x8*>(smem + (abase[i] + so) + p * PLANE_STRIDE);
@@ -276,13 +282,14 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_win_kernel(const Gathe
     constexpr int S = decltype(SET)::value;
     constexpr int t = decltype(T)::value;
     constexpr int ND = NB + (t < NWS ? 1 : 0);
-    constexpr int NM = TM * TN * 3;
+    constexpr int NM = TM * TN * PASSES;
+    static_assert(dma_slots_cover(NM, ND), "every stage issues each of its ND DMAs exactly once, window chunk first");
     constexpr int t3 = (t + 3) % 9;
     const int c3 = c + (t + 3) / 9;
 #pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      const int pa = (q == 0) ? 1 : 0;
-      const int pb = (q == 1) ? 1 : 0;
+    for (int q = 0; q < PASSES; ++q) {
+      const int pa = (PASSES == 3 && q == 0) ? 1 : 0;   // (one pass: h*h)
+      const int pb = (PASSES == 3 && q == 1) ? 1 : 0;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -291,7 +298,7 @@ __global__ __launch_bounds__(64 * WGM * WGN, 2) void conv_win_kernel(const Gathe
           const int idx = (q * TM + i) * TN + j;
 #pragma unroll
           for (int d = 0; d < ND; ++d)
-            if (idx == (((d + 1) * NM) / (ND + 1) > 0 ? ((d + 1) * NM) / (ND + 1) - 1 : 0)) {
+            if (idx == dma_slot(d, NM, ND)) {
               __builtin_amdgcn_sched_barrier(0);
               if (t < NWS && d == 0) issue_window(t, c + 1, (c + 1) & 1);
               else issue_filter(d - (t < NWS ? 1 : 0), c3, t3, t % 3);
@@ -762,6 +769,11 @@ template <int WGM, int NCH> constexpr auto win_streamk = &conv_win_kernel<WGM, N
 template <int WGM, int NCH> constexpr auto win_bnred = &conv_win_kernel<WGM, NCH, false, false, false, 2, 0, true>;   // fused BatchNorm-backward reduction
 template <int WGM, int NCH, int WGN> constexpr auto win_patch = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1>;
 template <int WGM, int NCH, int WGN> constexpr auto win_patch_bnred = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1, true>;
+// ... and their one-pass (h*h only) forms for the inference forward: never the BatchNorm-reduction or stamped ones
+template <int WGM, int NCH> constexpr auto win_plain_1p = &conv_win_kernel<WGM, NCH, false, false, false, 2, 0, false, 1>;
+template <int WGM, int NCH> constexpr auto win_split_1p = &conv_win_kernel<WGM, NCH, false, true, false, 2, 0, false, 1>;
+template <int WGM, int NCH> constexpr auto win_streamk_1p = &conv_win_kernel<WGM, NCH, false, false, true, 2, 0, false, 1>;
+template <int WGM, int NCH, int WGN> constexpr auto win_patch_1p = &conv_win_kernel<WGM, NCH, false, false, false, WGN, 1, false, 1>;
 
 template <int WGM, int NCH>
 static int launch_win(GatherConvArgs& a, hipStream_t st) {
@@ -776,6 +788,10 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
   a.nblocks = (int)nb;
   a.bwd_nslots = (int)tiles_m;
   YOLO_BNRED_CHECK(a)
+  if (a.one_pass && (a.stats != nullptr || a.bwd_y != nullptr || a.accumulate)) {
+    set_error("conv(window): one MFMA pass is an inference-forward form only");
+    return YOLO_ERR_INVALID_ARG;
+  }
   constexpr size_t lds = 2 * NCH * 4096 + 3 * 8192;
   const dim3 block(128 * WGM);
   // workgroups the chip holds at once (occupancy x CUs); 0 (a query failed): no stream-K
@@ -811,7 +827,9 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
     a.sk_grid = (int)(nb * a.split_parts);
     a.sk_slabs = conv_split_slabs();
     if constexpr (WGM == 2) {   // (conv_split_parts is asked for the 128-row tile only)
-      if (int rc = launch_lds<win_split<WGM, NCH>, lds>(dim3((unsigned)a.sk_grid), block, st, a, "conv_win_kernel(split)")) return rc;
+      const int rc = a.one_pass ? launch_lds<win_split_1p<WGM, NCH>, lds>(dim3((unsigned)a.sk_grid), block, st, a, "conv_win_kernel(split, one pass)")
+                                : launch_lds<win_split<WGM, NCH>, lds>(dim3((unsigned)a.sk_grid), block, st, a, "conv_win_kernel(split)");
+      if (rc) return rc;
     }
     return launch_split_reduce(a, BM, st);
   }
@@ -829,10 +847,14 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
     }
   }
   if constexpr (WGM == 2 && NCH == 5) {   // the one stamped instantiation (diagnostics on the 52x52 layers)
-    if (g_opt[OPT_STAMPS] != 0 && g_dbg_buf != nullptr && g_dbg_bytes >= (size_t)nb * 128) {
+    if (!a.one_pass && g_opt[OPT_STAMPS] != 0 && g_dbg_buf != nullptr && g_dbg_bytes >= (size_t)nb * 128) {
       a.stamps = reinterpret_cast<unsigned long long*>(g_dbg_buf);
       return launch_lds<win_stamped<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(stamps)");
     }
+  }
+  if (a.one_pass) {
+    if (a.sk_grid > 0) return launch_lds<win_streamk_1p<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(stream-K, one pass)");
+    return launch_lds<win_plain_1p<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(one pass)");
   }
   if (a.sk_grid > 0) return launch_lds<win_streamk<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel(stream-K)");
   return launch_lds<win_plain<WGM, NCH>, lds>(dim3(grid), block, st, a, "conv_win_kernel");
@@ -868,6 +890,13 @@ static int launch_patch(GatherConvArgs& a, hipStream_t st) {
   a.split_parts = 1;
   a.dbg = g_opt[OPT_DBG];
   const dim3 grid((unsigned)nb), block(64 * WGM * WGN);
+  if (a.one_pass) {
+    if (a.stats != nullptr || a.bwd_y != nullptr || a.accumulate) {
+      set_error("conv(patch window): one MFMA pass is an inference-forward form only");
+      return YOLO_ERR_INVALID_ARG;
+    }
+    return launch_lds<win_patch_1p<WGM, NCH, WGN>, lds>(grid, block, st, a, "conv_win_kernel(patch, one pass)");
+  }
   if (a.bwd_y == nullptr) return launch_lds<win_patch<WGM, NCH, WGN>, lds>(grid, block, st, a, "conv_win_kernel(patch)");
   return launch_lds<win_patch_bnred<WGM, NCH, WGN>, lds>(grid, block, st, a, "conv_win_kernel(patch, bn reduce)");
 }

@@ -15,6 +15,16 @@
 // of the exact bf16 x 6 split (conv_split.hip, still selectable: YOLO_CONV_PLANES=0), and the conv kernels
 // are bound by exactly that work (measured: 1.86x faster with half the passes).
 //
+// ONE PASS (PASSES == 1: the inference instantiations of conv_planes.hip, conv_win.hip, conv_small.hip behind the
+// yolo_conv2d_fwd_*_ex entry points with YOLO_PREC_F16). Only h*h is issued, i.e. the kernel computes the convolution of
+// the ROUNDED operands hx = fp16(s_x x) / s_x, hw = fp16(s_w w) / s_w, every product exact in the fp32 accumulator: against
+// the float64 convolution of (hx, hw) it has the accumulation error of the three-pass kernels and none of their dropped
+// terms; against the convolution of the unrounded operands it is off by fp16 operand rounding, 2^-11 relative per
+// element -- 2.6e-4 .. 4.5e-4 of max|y| on N(0,1) inputs with He-scaled filters, where three passes stay below 2e-5.
+// Operands whose l plane is zero (values fp16 represents after the scale) give bit-identical results in both modes.
+// The producers still write both planes and the DMA kernels still fetch both: only the fragment reads of l and two
+// thirds of the MFMAs are gone.
+//
 // Layout: 16-row blocks; inside a block one 1024-byte record per 16-channel block kb; inside a record four
 // 256-byte sub-blocks (plane p in {h, l}) x (k-half hf in {0, 1}), each 16 rows x 8 fp16:
 //     byte(row, c, p) = ((row>>4) * C/16 + c/16) * 1024 + (2*p + (c%16)/8) * 256 + (row&15) * 16 + (c%8)*2
@@ -38,6 +48,26 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 constexpr int PL_PLANES = 2;
 constexpr int PL_RECORD = 1024;  // bytes per (16-row block, 16-channel block): 2 planes x 2 halves x 256 B
 constexpr int PL_HEADER = 256;   // trailing header: bound bits, scale, 1/scale
+
+// MFMA passes per fragment pair: 3 (l*h + h*l + h*h, fp32-grade) or 1 (h*h only: fp16-rounded operands)
+template <int PASSES> constexpr int planes_frag_planes = PASSES == 1 ? 1 : PL_PLANES;   // planes a kernel reads from LDS
+constexpr bool planes_passes_ok(int passes) { return passes == 3 || passes == 1; }
+
+// A stage of the DMA kernels issues its ND DMA instructions between its NM MFMAs: DMA d goes behind MFMA number
+// dma_slot(d, NM, ND). Every d in [0, ND) must get a slot in [0, NM) and the slots must not decrease with d (the
+// hand-counted vmcnt immediates rely on the issue order) -- also when NM = 1 (one pass on a 32 x 32 wave tile), where
+// all of them land on MFMA 0.
+constexpr int dma_slot(int d, int NM, int ND) { return ((d + 1) * NM) / (ND + 1) > 0 ? ((d + 1) * NM) / (ND + 1) - 1 : 0; }
+constexpr bool dma_slots_cover(int NM, int ND) {
+  if (NM < 1) return false;
+  int prev = 0;
+  for (int d = 0; d < ND; ++d) {
+    const int s = dma_slot(d, NM, ND);
+    if (s < prev || s >= NM) return false;
+    prev = s;
+  }
+  return true;
+}
 
 __host__ __device__ inline long long planes_body_bytes(long long rows, int C) {
   return ((rows + 15) / 16 + 1) * (long long)(C / 16) * PL_RECORD;

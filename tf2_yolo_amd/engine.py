@@ -327,6 +327,7 @@ class Network:
         self.batch = None
         self.act = {}
         self.training = False
+        self._precision = "fp32"   # of the forward in progress: "fp16" = one MFMA pass, inference only (forward())
         self.grad_ready_hook = None   # called as hook(unit) after a unit's parameter grads are enqueued
         self.backward_begin_hook = None   # called at the start of backward (the gradient reducer's time origin)
         self._infer_scale_valid = False
@@ -547,7 +548,8 @@ class Network:
     def _conv_fwd(self, u, bias, out, stats=None, absmax=None):
         """the forward convolution of a conv / head unit: from planes where the unit has them, else the exact fp32 kernel"""
         if u.planes_fwd:
-            return ops.conv2d_fwd_planes(u.desc, self._xp(u.src), u.wp, bias, out=out, stats=stats, absmax=absmax)
+            return ops.conv2d_fwd_planes(u.desc, self._xp(u.src), u.wp, bias, out=out, stats=stats, absmax=absmax,
+                                         precision=self._precision)
         return ops.conv2d_fwd(u.desc, self.act[u.src.tid], self.params.view(u.p_kernel.name), bias, out=out, stats=stats,
                               absmax=absmax)
 
@@ -575,25 +577,28 @@ class Network:
         return True
 
     # ---- inference through a captured HIP graph ------------------------------------------------------------
-    def infer(self, x):
-        """forward(x, training=False) replayed from a hipGraph: a batch-1 forward is ~230 launches of a few
-        microseconds each, i.e. launch-bound when enqueued one by one. The graph is captured per batch size after an
-        eager pass (which also refreshes the filter planes and the folded BN scales) and dropped whenever the
-        parameters change. Outputs are the network's persistent head buffers, as with forward()."""
+    def infer(self, x, precision="fp32"):
+        """forward(x, training=False, precision=precision) replayed from a hipGraph: a batch-1 forward is ~230 launches of
+        a few microseconds each, i.e. launch-bound when enqueued one by one. The graph is captured per (batch size,
+        precision) after an eager pass (which also refreshes the filter planes and the folded BN scales) and dropped
+        whenever the parameters change. Outputs are the network's persistent head buffers, as with forward()."""
+        ops.precision_enum(precision)
         if not self._use_infer_graph:
-            return self.forward(x, training=False)
+            return self.forward(x, training=False, precision=precision)
         x = x.contiguous()
         N = x.shape[0]
-        g = self._infer_graphs.get(N)
+        # one graph per (batch size, precision); the fp32 graphs keep their bare batch-size key
+        key = N if precision == "fp32" else (N, precision)
+        g = self._infer_graphs.get(key)
         if g is None:
-            self.forward(x, training=False)                      # eager: allocations, weight prep, lazy module init
+            self.forward(x, training=False, precision=precision)   # eager: allocations, weight prep, lazy module init
             static_in = x.clone()
-            self.forward(static_in, training=False)
+            self.forward(static_in, training=False, precision=precision)
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
-                outs = self.forward(static_in, training=False)
-            g = self._infer_graphs[N] = (graph, static_in, outs)
+                outs = self.forward(static_in, training=False, precision=precision)
+            g = self._infer_graphs[key] = (graph, static_in, outs)
         graph, static_in, outs = g
         static_in.copy_(x)
         graph.replay()
@@ -617,9 +622,14 @@ class Network:
         self._infer_scale_valid = False
 
     # ---- forward ------------------------------------------------------------------------
-    def forward(self, x, training=False, stop_after=None):
+    def forward(self, x, training=False, stop_after=None, precision="fp32"):
         """x: float32 CUDA tensor [N,H,W,C]. Returns the list of head outputs (coarse -> fine).
-        stop_after (benchmarks only: bench.py's Darknet-53 block): name of the unit behind which the pass ends; returns None."""
+        stop_after (benchmarks only: bench.py's Darknet-53 block): name of the unit behind which the pass ends; returns None.
+        precision: "fp32" (three MFMA passes per planes convolution) or, inference only, "fp16" (one pass on the fp16-rounded
+        operands; the stem and the convolutions without planes operands stay exact)."""
+        ops.precision_enum(precision)
+        if training and precision != "fp32":
+            raise ValueError("forward(training=True) is fp32-grade only: precision='fp16' is an inference mode")
         if x.dtype != torch.float32 or not x.is_cuda:
             raise YoloHipError("forward expects a float32 CUDA tensor")
         x = x.contiguous()
@@ -628,6 +638,7 @@ class Network:
                                f"{(self.input.h, self.input.w, self.input.c)}")
         self.allocate(x.shape[0])
         self.training = training
+        self._precision = precision
         self.act[self.input.tid] = x
         self._xp_valid = set()
         self._tbound_set = set()
@@ -745,7 +756,8 @@ class Network:
     def _fwd_head(self, u, training):
         bias, anchors = self.params.view(u.p_bias.name), self._anchors_dev.get(u.name)
         if not training and self._infer_small_fuse and self._fuse_infer and u.planes_fwd:
-            ops.conv2d_fwd_head_unit(u.desc, self._xp(u.src), u.wp, bias, u.A, u.C, u.version, anchors, u.t, u.yact)
+            ops.conv2d_fwd_head_unit(u.desc, self._xp(u.src), u.wp, bias, u.A, u.C, u.version, anchors, u.t, u.yact,
+                                     precision=self._precision)
             return
         self._conv_fwd(u, bias, u.t)
         ops.head_act_fwd(u.t, u.A, u.C, u.version, anchors, out=u.yact)
@@ -852,7 +864,7 @@ class Network:
             nw = ops.conv2d_fwd_infer_unit(u.desc, self._xp(u.src), u.wp, bias, _epilogue(u), scale, shift, res, u.a, u.amax,
                                            u.pred, self._tb_words(src_slot),
                                            self._tb_words(u.residual.tid) if u.residual is not None else None, pl,
-                                           self._tb_row(u.out.tid), self._tb[u.out.tid])
+                                           self._tb_row(u.out.tid), self._tb[u.out.tid], precision=self._precision)
             if nw:
                 self._tword_n[u.out.tid] = nw
             self._tbound_set.add(u.out.tid)
@@ -862,7 +874,7 @@ class Network:
         if not own_planes:
             return False
         ops.conv2d_fwd_planes_epi(u.desc, self._xp(u.src), u.wp, bias, _epilogue(u), scale, shift, residual=res, out=u.a,
-                                  absmax=u.amax)
+                                  absmax=u.amax, precision=self._precision)
         ops.split_planes_absmax(u.a, self.batch * u.out.h * u.out.w, u.cout, u.amax, pl,
                                 extra_bound=self._tb_float(u.residual.tid) if u.residual is not None else None,
                                 out_bound=self._tb[u.out.tid])

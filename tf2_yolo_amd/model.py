@@ -12,7 +12,7 @@ import torch
 
 from . import dp as dp_mod
 from . import optimizers as opt_mod
-from ._lib import YoloHipError
+from ._lib import YoloHipError, precision_enum
 from .engine import Network
 
 
@@ -257,7 +257,11 @@ class Model:
         outs = [t.clone() for t in self.net.forward(_to_input(x), training=training)]
         return outs[0] if self.single_output else outs
 
-    def predict(self, x, batch_size=32, verbose=0, **_):
+    def predict(self, x, batch_size=32, verbose=0, precision="fp32", **_):
+        """precision: "fp32" (default) or "fp16" -- half-precision inference: every planes convolution runs ONE fp16 MFMA
+        pass on its fp16-rounded operands (outputs off by ~3e-4 of their largest entry; DESIGN.md, half-precision
+        inference). __call__ and evaluate stay fp32."""
+        precision_enum(precision)   # ValueError on anything else (unknown keywords are otherwise ignored here)
         if hasattr(x, "__getitem__") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor)):
             chunks = [x[i][0] for i in range(len(x))]     # Sequence of (img, label) batches
         else:
@@ -265,7 +269,7 @@ class Model:
             chunks = [x[i:i + batch_size] for i in range(0, n, batch_size)]
         outs = None
         for c in chunks:
-            o = self.net.infer(_to_input(c))
+            o = self.net.infer(_to_input(c), precision=precision)
             o = [t.cpu().numpy() for t in o]
             outs = [[a] for a in o] if outs is None else [acc + [a] for acc, a in zip(outs, o)]
         res = [np.concatenate(a, axis=0) for a in outs]

@@ -428,7 +428,13 @@ class BatchJobs:
         check(fn(_p(self.table), len(self.rows), self.blocks, _stream()), "yolo_%s_batch" % self.kind)
 
 
-def conv2d_fwd_planes(d, xp, wp, bias=None, out=None, stats=None, absmax=None):
+precision_enum = _lib.precision_enum   # "fp32" / "fp16" -> YOLO_PREC_*; ValueError on anything else
+
+
+def conv2d_fwd_planes(d, xp, wp, bias=None, out=None, stats=None, absmax=None, precision="fp32"):
+    """precision (here and in the three inference forms below): "fp32" = three MFMA passes, "fp16" = the h*h pass alone
+    (inference only: include/yolo_hip.h, yolo_conv2d_fwd_planes_ex)"""
+    prec = precision_enum(precision)
     _chk_f32(bias)
     if out is None:
         out = torch.empty((d.N, d.Ho, d.Wo, d.Cout), device=xp.device, dtype=torch.float32)
@@ -439,8 +445,8 @@ def conv2d_fwd_planes(d, xp, wp, bias=None, out=None, stats=None, absmax=None):
     if stats is not None and stats.numel() != BN_STAT_SLOTS * 2 * d.Cout:
         raise YoloHipError("conv2d_fwd_planes: stats must hold BN_STAT_SLOTS x 2 x Cout doubles")
     def run():
-        check(_lib.load().yolo_conv2d_fwd_planes(byref(d), _p(xp), _p(wp), _p(bias), _p(out), _p(stats), _p(absmax),
-                                                 _stream()), "yolo_conv2d_fwd_planes")
+        check(_lib.load().yolo_conv2d_fwd_planes_ex(byref(d), _p(xp), _p(wp), _p(bias), _p(out), _p(stats), _p(absmax),
+                                                    prec, _stream()), "yolo_conv2d_fwd_planes_ex")
     if TIMER is not None:
         TIMER.bracket(_planes_variant(d.Cout, _win_key(d, d.H, d.W, d.Cin), d.kh * d.kw == 1), _conv_flops(d), 1, run,
                       _layer_key(d, "fwd"))
@@ -452,9 +458,10 @@ def conv2d_fwd_planes(d, xp, wp, bias=None, out=None, stats=None, absmax=None):
 EPI_NONE, EPI_AFFINE, EPI_AFFINE_LEAKY, EPI_AFFINE_MISH = 0, 1, 2, 3   # include/yolo_hip.h YOLO_EPI_*
 
 
-def conv2d_fwd_planes_epi(d, xp, wp, bias, epilogue, scale, shift, residual=None, out=None, absmax=None):
-    """inference: out = act(scale * (conv + bias) + shift) (+ residual) in ONE kernel (yolo_conv2d_fwd_planes_epi);
+def conv2d_fwd_planes_epi(d, xp, wp, bias, epilogue, scale, shift, residual=None, out=None, absmax=None, precision="fp32"):
+    """inference: out = act(scale * (conv + bias) + shift) (+ residual) in ONE kernel (yolo_conv2d_fwd_planes_epi_ex);
     absmax: per-channel max|out| before the residual (bit patterns, zeroed by the caller)"""
+    prec = precision_enum(precision)
     _chk_f32(bias, scale, shift, residual)
     if out is None:
         out = torch.empty((d.N, d.Ho, d.Wo, d.Cout), device=xp.device, dtype=torch.float32)
@@ -463,9 +470,9 @@ def conv2d_fwd_planes_epi(d, xp, wp, bias, epilogue, scale, shift, residual=None
     if out.numel() != d.N * d.Ho * d.Wo * d.Cout or (residual is not None and residual.numel() != out.numel()):
         raise YoloHipError("conv2d_fwd_planes_epi: output / residual size does not match the descriptor")
     def run():
-        check(_lib.load().yolo_conv2d_fwd_planes_epi(byref(d), _p(xp), _p(wp), _p(bias), int(epilogue), _p(scale), _p(shift),
-                                                     _p(residual), _p(out), _p(absmax), _stream()),
-              "yolo_conv2d_fwd_planes_epi")
+        check(_lib.load().yolo_conv2d_fwd_planes_epi_ex(byref(d), _p(xp), _p(wp), _p(bias), int(epilogue), _p(scale), _p(shift),
+                                                        _p(residual), _p(out), _p(absmax), prec, _stream()),
+              "yolo_conv2d_fwd_planes_epi_ex")
     if TIMER is not None:
         TIMER.bracket(_planes_variant(d.Cout, _win_key(d, d.H, d.W, d.Cin), d.kh * d.kw == 1), _conv_flops(d), 1, run,
                       _layer_key(d, "fwd"))
@@ -488,10 +495,11 @@ INFER_BOUND_WORDS = 4096   # YOLO_INFER_BOUND_WORDS in include/yolo_hip.h
 
 
 def conv2d_fwd_infer_unit(d, xp, wp, bias, epilogue, scale, shift, residual, out, absmax, pred2, in_bound, residual_bound,
-                          planes, out_words, out_bound):
-    """inference conv-BN-activation(-Add) unit whose result also leaves as planes (yolo_conv2d_fwd_infer_unit). in_bound /
+                          planes, out_words, out_bound, precision="fp32"):
+    """inference conv-BN-activation(-Add) unit whose result also leaves as planes (yolo_conv2d_fwd_infer_unit_ex). in_bound /
     residual_bound: 1 float or the words another such unit left. Returns the number of words of out_words that now hold
     max|result| (one pass), or 0 when the bound is the float out_bound (two passes inside the call)."""
+    prec = precision_enum(precision)
     _chk_f32(bias, scale, shift, residual, out, pred2, out_bound)
     if xp.numel() < planes_bytes(d.N * d.H * d.W, d.Cin) or wp.numel() < planes_bytes(d.Cout, d.kh * d.kw * d.Cin):
         raise YoloHipError("conv2d_fwd_infer_unit: planes buffers do not match the descriptor")
@@ -503,12 +511,12 @@ def conv2d_fwd_infer_unit(d, xp, wp, bias, epilogue, scale, shift, residual, out
         if b is not None and (not 1 <= b.numel() <= INFER_BOUND_WORDS or b.element_size() != 4):
             raise YoloHipError("conv2d_fwd_infer_unit: a bound is 1..4096 four-byte words")
     n = ctypes.c_int(0)
-    check(_lib.load().yolo_conv2d_fwd_infer_unit(byref(d), _p(xp), _p(wp), _p(bias), int(epilogue), _p(scale), _p(shift),
-                                                 _p(residual), _p(out), _p(absmax), _p(pred2), _p(in_bound),
-                                                 int(in_bound.numel()), _p(residual_bound),
-                                                 int(residual_bound.numel()) if residual_bound is not None else 0,
-                                                 _p(planes), _p(out_words), _p(out_bound), byref(n), _stream()),
-          "yolo_conv2d_fwd_infer_unit")
+    check(_lib.load().yolo_conv2d_fwd_infer_unit_ex(byref(d), _p(xp), _p(wp), _p(bias), int(epilogue), _p(scale), _p(shift),
+                                                    _p(residual), _p(out), _p(absmax), _p(pred2), _p(in_bound),
+                                                    int(in_bound.numel()), _p(residual_bound),
+                                                    int(residual_bound.numel()) if residual_bound is not None else 0,
+                                                    _p(planes), _p(out_words), _p(out_bound), byref(n), prec, _stream()),
+          "yolo_conv2d_fwd_infer_unit_ex")
     return int(n.value)
 
 
@@ -613,17 +621,19 @@ def split_planes_concat_ex(srcs, channels, bounds, rows, planes, upsample=None, 
     return planes
 
 
-def conv2d_fwd_head_unit(d, xp, wp, bias, A, C, version, anchors_dev, t, y):
+def conv2d_fwd_head_unit(d, xp, wp, bias, A, C, version, anchors_dev, t, y, precision="fp32"):
     """detection head: t = 1x1 convolution (+ bias) on planes operands, y = the head's activation of t; one launch where the
-    launch has few output pixels (include/yolo_hip.h: yolo_conv2d_fwd_head_unit)"""
+    launch has few output pixels (include/yolo_hip.h: yolo_conv2d_fwd_head_unit_ex)"""
+    prec = precision_enum(precision)
     _chk_f32(t, y)
     n = d.N * d.Ho * d.Wo * d.Cout
     if t.numel() != n or y.numel() != n:
         raise YoloHipError("conv2d_fwd_head_unit: output size does not match the descriptor")
     if xp.numel() < planes_bytes(d.N * d.H * d.W, d.Cin) or wp.numel() < planes_bytes(d.Cout, d.kh * d.kw * d.Cin):
         raise YoloHipError("conv2d_fwd_head_unit: planes buffers do not match the descriptor")
-    check(_lib.load().yolo_conv2d_fwd_head_unit(ctypes.byref(d), _p(xp), _p(wp), _p(bias), int(A), int(C), int(version),
-                                                _p(anchors_dev), _p(t), _p(y), _stream()), "yolo_conv2d_fwd_head_unit")
+    check(_lib.load().yolo_conv2d_fwd_head_unit_ex(ctypes.byref(d), _p(xp), _p(wp), _p(bias), int(A), int(C), int(version),
+                                                   _p(anchors_dev), _p(t), _p(y), prec, _stream()),
+          "yolo_conv2d_fwd_head_unit_ex")
     return y
 
 
