@@ -75,6 +75,14 @@ enum { YOLO_OPT_CONV_WIN = 0, YOLO_OPT_STAMPS = 1, YOLO_OPT_CONV_SK = 2, YOLO_OP
                           64-channel chunk ahead instead of one cell ahead, 16 = forward convolutions with BatchNorm statistics are
                           never split over several workgroups (as until round 5) */ };
 int yolo_set_option(int key, int value);
+/* Which kernel the convolution entry points launched on the calling thread (no reference counterpart; reports and profilers
+ * label their timings with it). Returns the family of the newest MAIN convolution launch since the previous call of this
+ * function -- "gather_conv_planes_kernel<128,128,2,2>", "conv_win_planes_kernel<128,128>", "wgrad_kernel", ...: the kernel's
+ * name and leading tile / wave arguments -- in a per-thread buffer that the next call overwrites, and "" when there was none.
+ * *launches_host (optional, HOST pointer) receives the number of such launches since the previous call (a stride-2
+ * yolo_conv2d_dgrad is one per parity class); reduce kernels, bias sums and planes passes are not counted. A host-side note:
+ * the call enqueues nothing and never fails. */
+const char* yolo_last_conv_kernel(int* launches_host);
 /* Scratch for the split-K / stream-K forms of the planes convolutions (key 2 = YOLO_OPT_CONV_SK != 0): the accumulator
  * slabs of tiles computed by several workgroups (+ the stream-K form's tile tickets). The caller owns the memory
  * (yolo_conv_workspace_bytes() bytes, device); the call zeroes the ticket area on `stream`. ONE workspace per process:

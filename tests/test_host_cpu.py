@@ -30,6 +30,21 @@ def test_library_exports_every_declared_symbol():
     assert loaded.yolo_device_available() in (0, 1)
 
 
+def test_last_conv_kernel_query_before_any_launch():
+    """yolo_last_conv_kernel: no launch noted -> "" and 0 launches; a host-side question that never lands on a launch tape"""
+    from tf2_yolo_amd import _lib
+    lib = _lib.load()
+    import torch
+    n = ctypes.c_int(-1)
+    first = lib.yolo_last_conv_kernel(ctypes.byref(n))
+    if not torch.cuda.is_available():     # (with a GPU, earlier tests of this process have launched: the call above forgets them)
+        assert first == b"" and n.value == 0
+    n.value = -1
+    assert lib.yolo_last_conv_kernel(ctypes.byref(n)) == b"" and n.value == 0
+    assert lib.yolo_last_conv_kernel(None) == b""
+    assert "yolo_last_conv_kernel" in _lib._QUERIES and not isinstance(lib.yolo_last_conv_kernel, _lib._Recorded)
+
+
 def test_architecture_cross_checks():
     """SURVEY.md Appendix A / BASELINE.md section 3: parameter counts and forward FLOPs derived from the graph
     definitions equal the publicly known Darknet / keras-yolo3 figures."""

@@ -54,6 +54,7 @@ SIGNATURES = {
     "yolo_abi_version": (c_int, []),
     "yolo_device_available": (c_int, []),
     "yolo_set_option": (c_int, [c_int, c_int]),
+    "yolo_last_conv_kernel": (c_char_p, [POINTER(c_int)]),
     "yolo_mfma_probe": (c_int, [_P, _P, c_int, c_int, POINTER(c_double), _P]),
     "yolo_set_debug_buffer": (c_int, [_P, c_size_t]),
     "yolo_encode_labels": (c_int, [_P, _P, _P, c_int, c_double, c_double, c_int, c_int, c_int, _P, _P, _P]),
@@ -169,7 +170,7 @@ SIGNATURES = {
 _lib = None
 
 # functions that only answer a question on the host: never part of a recorded step (tape.py)
-_QUERIES = {"yolo_last_error", "yolo_abi_version", "yolo_bnred_slots_cap", "yolo_device_available", "yolo_conv_workspace_bytes", "yolo_planes_bytes",
+_QUERIES = {"yolo_last_error", "yolo_last_conv_kernel", "yolo_abi_version", "yolo_bnred_slots_cap", "yolo_device_available", "yolo_conv_workspace_bytes", "yolo_planes_bytes",
             "yolo_stem_bwd_scratch_bytes", "yolo_loss_workspace_bytes", "yolo_decode_workspace_bytes",
             "yolo_nms_workspace_bytes", "yolo_pr_curve_workspace_bytes", "yolo_wgrad_workspace_bytes", "yolo_adam_lr_t",
             "yolo_grad_sqnorm_workspace_bytes",

@@ -355,6 +355,7 @@ static int launch_gather(GatherConvArgs& a, hipStream_t st) {
   }
   a.nblocks = (int)nb;
   constexpr size_t lds = 2 * (BM + BN) * 36 * sizeof(float);
+  note_conv_launch(FLAT ? "gather_conv_kernel<%d,%d,flat>" : "gather_conv_kernel<%d,%d>", BM, BN);
   return launch_lds<gather_conv_kernel<BM, BN, WGM, WGN, FLAT>, lds>(dim3((unsigned)nb), dim3(256), st, a, "gather_conv_kernel");
 }
 
@@ -720,6 +721,7 @@ static int launch_wgrad(WgradArgs& a, hipStream_t st) {
     return YOLO_ERR_INVALID_ARG;
   }
   constexpr size_t lds = 2 * 32 * (BM + BN) * sizeof(float);
+  note_conv_launch("wgrad_kernel");   // (one name for all of its tiles)
   hipLaunchKernelGGL((wgrad_kernel<BM, BN, WGM, WGN, ASCALAR, BSCALAR>), dim3((unsigned)tiles, (unsigned)splits),
                      dim3(NT), lds, st, a);
   if (int rc = check_launch("wgrad_kernel")) return rc;

@@ -181,6 +181,10 @@ extern void* g_dbg_buf;        // yolo_set_debug_buffer
 extern size_t g_dbg_bytes;
 extern int g_opt[OPT_COUNT];
 void init_options();
+// What this thread launched last (runtime.hip, read by yolo_last_conv_kernel): every templated launcher calls this where it
+// launches its MAIN kernel -- family = a printf format (a string literal) for up to four ints, formatted only when asked for.
+// The reduce kernels, the bias column sums and the planes passes are helpers and leave no note.
+void note_conv_launch(const char* family, int a = 0, int b = 0, int c = 0, int d = 0);
 // conv_wgrad_planes.hip
 int launch_wgrad_planes(WgradArgs& a, hipStream_t st);
 bool wgrad_planes_supported(const WgradArgs& a);

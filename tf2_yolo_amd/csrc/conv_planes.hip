@@ -544,6 +544,7 @@ static int launch_planes(GatherConvArgs& a, hipStream_t st) {
     set_error("conv(planes): bad grid %lld", nb);
     return YOLO_ERR_INVALID_ARG;
   }
+  note_conv_launch("gather_conv_planes_kernel<%d,%d,%d,%d>", BM, BN, WGM, WGN);   // (every form below: one family)
   constexpr size_t lds = (3 + ((FORM >> 7) & 3)) * (BM / 32 + BN / 32) * PL_PLANES * 1024;
   const dim3 block(64 * WGM * WGN);
   if constexpr (FORM == 0) {

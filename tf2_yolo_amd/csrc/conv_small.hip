@@ -409,6 +409,7 @@ template <int NT, int TM, int TN, int CH, bool HEAD = false>
 static int launch_small(GatherConvArgs& a, hipStream_t st, int* nwg) {
   a.nblocks = (int)(((a.M + 32 * TM - 1) / (32 * TM)) * ((a.Cout + 32 * TN - 1) / (32 * TN)));
   *nwg = a.nblocks;
+  note_conv_launch("conv_small_planes_kernel<%d,%d>", 32 * TM, 32 * TN);
   if (a.one_pass)   // (the same tile and grid: small_tile / small_head_tile never look at the precision)
     return launch_lds<conv_small_kernel<NT, TM, TN, CH, HEAD, 1>, SmallLds<TM, TN, NT>::BYTES>(dim3((unsigned)a.nblocks), dim3(64 * SM_WAVES),
                                                                                               st, a, "conv_small_kernel(one pass)");

@@ -323,6 +323,7 @@ static int launch_split(GatherConvArgs& a, hipStream_t st) {
   }
   a.nblocks = (int)nb;
   constexpr size_t lds = 2 * 3 * (BM + BN) * SPLIT_ROW * sizeof(unsigned short);
+  note_conv_launch("gather_conv_split_kernel<%d,%d,%d,%d>", BM, BN, WGM, WGN);
   return launch_lds<gather_conv_split_kernel<BM, BN, WGM, WGN>, lds>(dim3((unsigned)nb), dim3(64 * WGM * WGN), st, a,
                                                                      "gather_conv_split_kernel");
 }

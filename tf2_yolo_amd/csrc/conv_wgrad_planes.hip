@@ -399,6 +399,7 @@ static int launch_wp(WgradArgs& a, hipStream_t st) {
     return YOLO_ERR_INVALID_ARG;
   }
   a.nblocks = (int)(tiles * splits);
+  note_conv_launch("wgrad_planes_kernel<%d,%d,%d,%d>", BM, BN, WGM, WGN);
   if (int rc = launch_lds<kernel, lds>(dim3((unsigned)(tiles * splits)), dim3(64 * WGM * WGN), st, a, "wgrad_planes_kernel")) return rc;
   if (a.slabs != nullptr) {
     const long long pieces = tiles * (BM * BN / 4);

@@ -275,6 +275,7 @@ static int launch_ws(WgradArgs& a, hipStream_t st) {
     return YOLO_ERR_INVALID_ARG;
   }
   constexpr size_t lds = 2 * 3 * 16 * (row_stride_bf16(BM) + row_stride_bf16(BN)) * sizeof(unsigned short);
+  note_conv_launch("wgrad_split_kernel<%d,%d,%d,%d>", BM, BN, WGM, WGN);
   hipLaunchKernelGGL((wgrad_split_kernel<BM, BN, WGM, WGN>), dim3((unsigned)tiles, (unsigned)splits), dim3(256), lds, st,
                      a);
   return check_launch("wgrad_split_kernel");

@@ -917,6 +917,7 @@ static int launch_ww(WgradArgs& a, hipStream_t st) {
   // (one split -- the small layers of a small batch -- still goes through its slab: measured round 6, a tile's owner adding
   // to dw itself with scalar read-modify-writes costs the kernel what the slab + reduce launch cost: 44 vs 25 + 17 us, and
   // the 128 x 256 per-tap tile 103 vs 22 + 27 us)
+  note_conv_launch(M16 ? "wgrad_win_planes_kernel<%d,%d,mfma16>" : "wgrad_win_planes_kernel<%d,%d>", WW_CO, 9 * WW_CI);
   if (int rc = launch_lds<kernel, lds>(dim3((unsigned)a.nblocks), dim3(256), st, a, "wgrad_win_kernel")) return rc;
   if (a.slabs != nullptr) {
     const long long pieces = tiles * (WW_TILE_FLOATS / 4);
@@ -958,6 +959,7 @@ static int launch_ww2(WgradArgs& a, hipStream_t st) {
   a.chunk = chunk;
   a.splits = (int)splits;
   a.nblocks = (int)(tiles * splits);
+  note_conv_launch("wgrad_win_planes_kernel<%d,%d>", WW_CO, 9 * WW_CI);   // (the two-half form: the family's plain name)
   if (int rc = launch_lds<kernel, lds>(dim3((unsigned)a.nblocks), dim3(512), st, a, "wgrad_win2_kernel")) return rc;
   const long long pieces = tiles * (WW_TILE_FLOATS / 4);
   hipLaunchKernelGGL(wgrad_win_reduce_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, st, a);

@@ -792,6 +792,7 @@ static int launch_win(GatherConvArgs& a, hipStream_t st) {
     set_error("conv(window): one MFMA pass is an inference-forward form only");
     return YOLO_ERR_INVALID_ARG;
   }
+  note_conv_launch("conv_win_planes_kernel<%d,128>", BM);
   constexpr size_t lds = 2 * NCH * 4096 + 3 * 8192;
   const dim3 block(128 * WGM);
   // workgroups the chip holds at once (occupancy x CUs); 0 (a query failed): no stream-K
@@ -884,6 +885,7 @@ static int launch_patch(GatherConvArgs& a, hipStream_t st) {
   a.nblocks = (int)nb;
   a.bwd_nslots = (int)tiles_m;
   YOLO_BNRED_CHECK(a)
+  note_conv_launch("conv_patch_planes_kernel<%d,%d>", BM, BN);
   constexpr size_t lds = 2 * NCH * 4096 + 3 * 4096 * WGN;
   a.tile_order = 0;   // column tile fastest: the column tiles of a patch share its window in L2
   a.sk_grid = 0;

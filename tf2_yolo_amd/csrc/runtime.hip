@@ -14,6 +14,14 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
+// The main convolution launches of this thread since the last yolo_last_conv_kernel: the family of the newest, their number
+static thread_local struct { const char* family; int v[4]; int launches; } g_conv_note = {"", {0, 0, 0, 0}, 0};
+static thread_local char g_conv_name[96] = "";
+
+void note_conv_launch(const char* family, int a, int b, int c, int d) {
+  g_conv_note = {family, {a, b, c, d}, g_conv_note.launches + 1};
+}
+
 // Run-time options. Index = OPT_* (conv_args.hpp); defaults come from the environment once, yolo_set_option
 // overrides them (benchmarks switch kernel variants inside one process: rule "A/B in one process").
 int g_opt[OPT_COUNT];
@@ -74,6 +82,14 @@ extern "C" int yolo_set_debug_buffer(void* p, size_t bytes) {
 }
 
 extern "C" const char* yolo_last_error(void) { return yolo::g_err; }
+
+extern "C" const char* yolo_last_conv_kernel(int* launches) {
+  auto& n = yolo::g_conv_note;
+  snprintf(yolo::g_conv_name, sizeof(yolo::g_conv_name), n.family, n.v[0], n.v[1], n.v[2], n.v[3]);
+  if (launches != nullptr) *launches = n.launches;
+  n = {"", {0, 0, 0, 0}, 0};
+  return yolo::g_conv_name;
+}
 
 extern "C" int yolo_abi_version(void) { return 5; }   // 5: round 6 added yolo_bn_act_bwd_reduce_fold_ld (the reduction finished by its own launch), option key 8 (timing experiments), yolo_maxpool2x2_bwd, yolo_bn_act_maxpool2x2_fwd, yolo_split_planes_concat_ex, yolo_conv2d_fwd_head_unit; 4: round 5 added yolo_conv2d_dgrad_planes_bnred, yolo_bn_act_bwd_sum_partials, yolo_bnred_slots_cap, option key 7, yolo_allreduce_bucket; 3: round 4 added yolo_bn_act_bwd_reduce_bound_ld / _apply_planes_ld (dout with a row pitch), option key 6; 2: round 3 added yolo_cal_iou, yolo_nms_select, yolo_adam_step_dev, yolo_bn_finalize_offset, the wgrad workspace, yolo_mfma_probe
 

@@ -506,6 +506,7 @@ int launch_stem_fwd(const yolo_conv_desc* d, const float* x, const float* w, con
   int grid = (M + 255) / 256;
   if (grid > per_cu[st_on] * cus) grid = per_cu[st_on] * cus;
   const int mfma = stem_mfma_per_cu();
+  note_conv_launch("stem_conv3x3_kernel");   // (the family's name, the matrix-core form included)
   if (sreg && mfma) {
     float* wt = wt_ring + (size_t)(wt_next++ & 7) * (STEM_K + 1) * STEM_CO;
     hipLaunchKernelGGL(stem_filter_prep_kernel, dim3(1), dim3(256), 0, st, w, bias, wt);
@@ -565,6 +566,7 @@ int launch_stem_bn_bwd_wgrad(const yolo_conv_desc* d, const float* y, const floa
   long long grid = (P / 16 + 3) / 4;
   if (grid > STEM_BWD_GRID) grid = STEM_BWD_GRID;
   if (grid < 1) grid = 1;
+  note_conv_launch("stem_bn_bwd_wgrad_kernel");
   hipLaunchKernelGGL(stem_bn_bwd_wgrad_kernel, dim3((unsigned)grid), dim3(256), 0, st, y, dout, img, P, d->H, d->W, d->pad_t,
                      d->pad_l, 1.0 / (double)P, scale, shift, smean, sinv, act, redsum, dgamma, dbeta, scratch);
   hipLaunchKernelGGL(stem_wgrad_sum_kernel, dim3(16), dim3(1024), 0, st, scratch, (int)grid, dw);

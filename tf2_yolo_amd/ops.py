@@ -23,17 +23,23 @@ SPLIT_BATCH_UNITS = 4   # include/yolo_hip.h YOLO_SPLIT_BATCH_UNITS
 class KernelTimer:
     """Brackets the MFMA conv launches with HIP events on the launch stream (bench.py roofline).
     Aggregates per kernel variant: launches, device time, algorithmic FLOPs (2*M*N*K, no padding,
-    im2col or recompute credit). Enabled by assigning an instance to `ops.TIMER`."""
+    im2col or recompute credit). The variant's name and the number of its launches are what the library says it
+    launched (include/yolo_hip.h: yolo_last_conv_kernel). Enabled by assigning an instance to `ops.TIMER`."""
 
     def __init__(self):
         self.pending = []
 
-    def bracket(self, name, flops, launches, fn, layer=None):
+    def bracket(self, flops, fn, layer=None):
+        last, n = _lib.load().yolo_last_conv_kernel, ctypes.c_int(0)
+        last(None)     # forget what ran before the bracket
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         s.record()
         fn()
         e.record()
-        self.pending.append((name, flops, launches, s, e, layer))
+        name = last(byref(n)).decode()
+        if not name:
+            raise YoloHipError("KernelTimer: the bracketed call launched no convolution kernel")
+        self.pending.append((name, flops, n.value, s, e, layer))
 
     def summary(self, by_layer=False):
         """per kernel variant (default) or per (kernel variant, layer) -- layer = (pass, H, W, Cin, Cout, k, stride, N)"""
@@ -77,85 +83,6 @@ def planes_dgrad_ok(cin, cout):
 def planes_wgrad_ok(cin, cout, taps, stride=1):
     # (stride is not a criterion: stride-2 filter gradients run on the planes kernel too)
     return USE_PLANES and cin % 16 == 0 and cout % 16 == 0 and cout >= 32 and taps * cin >= 64
-
-
-_WGRAD_WIDE = int(_os.environ.get("YOLO_WGRAD_WIDE", "2"))
-
-
-WGRAD_WIN = int(_os.environ.get("YOLO_WGRAD_WIN", "1"))
-
-
-def _wgrad_win_covers(d):
-    """mirrors wgrad_win_supported() in csrc/conv_wgrad_win.hip: 3x3 stride-1 'same', 128-filter x 32-channel tiles,
-    at least 64 and fewer than 2^31 - 4096 pixels (WGRAD_WIN follows set_option / reset_options)"""
-    m = d.N * d.Ho * d.Wo
-    return (WGRAD_WIN != 0 and d.kh == 3 and d.kw == 3 and d.sh == 1 and d.sw == 1 and d.pad_t == 1 and d.pad_l == 1
-            and d.H == d.Ho and d.W == d.Wo and d.Cout % 128 == 0 and d.Cin % 32 == 0 and d.W >= 4
-            and 2 * d.W + 81 <= 512 and 32 // d.W + 2 <= d.H and 64 <= m < (1 << 31) - 4096)
-
-
-def _wgrad_planes_variant(cout, cols, taps=1, pixels=1 << 40, d=None):
-    """mirrors launch_wgrad_planes() in csrc/conv_wgrad_planes.hip (names used by bench.py's roofline report)"""
-    if d is not None and _wgrad_win_covers(d):
-        # conv_wgrad_win.hip: 128 filters x (9 taps x 32 channels) per workgroup, x streamed once through an LDS ring
-        return "wgrad_win_planes_kernel<128,288%s>" % (",mfma16" if WGRAD_WIN == 3 else "")
-    if cout > 64 and cols >= 256 and (_WGRAD_WIDE == 1 or (_WGRAD_WIDE == 2 and taps > 1 and pixels <= 8192)):
-        return "wgrad_planes_kernel<128,256,2,2>"
-    big = "4,2" if _os.environ.get("YOLO_WGRAD_WAVES") == "8" else "2,2"
-    return "wgrad_planes_kernel<%d,%d,%s>" % (64 if cout <= 64 else 128, 64 if cols <= 64 else 128,
-                                             "2,2" if (cout <= 64 and cols <= 64) else "2,4" if cout <= 64
-                                             else "4,2" if cols <= 64 else big)
-
-
-_PLANES_WAVES = int(_os.environ.get("YOLO_PLANES_WAVES", "0") or 0)   # 0: the library's automatic choice
-
-
-CONV_WIN = int(_os.environ.get("YOLO_CONV_WIN", "1"))
-CONV_PATCH = int(_os.environ.get("YOLO_CONV_PATCH", "1"))
-
-
-def _planes_variant(cout, win=None, k1=False):
-    """mirrors launch_gather_planes() in csrc/conv_planes.hip and launch_conv_win() in csrc/conv_win.hip;
-    win = (W of the source, M rows) of a 3x3 stride-1 layer, None otherwise; k1 = 1x1 stride-1 layer (8-wave tile)"""
-    if win is not None and CONV_WIN not in (0, 2, 4) and CONV_PATCH and cout >= 64:
-        # launch_conv_patch() in csrc/conv_win.hip: rows longer than 64 pixels or Cout <= 64, at least 256 tiles
-        ws, m, hs, n = win
-        narrow = cout <= 64
-        tiles = (n * ((hs + 15) // 16) * ((ws + 15) // 16) if narrow
-                 else n * ((hs + 7) // 8) * ((ws + 15) // 16) * ((cout + 127) // 128))
-        if CONV_PATCH == 2 or ((narrow or ws > 64) and tiles >= 256):
-            return "conv_patch_planes_kernel<%s>" % ("256,64" if narrow else "128,128")
-    if win is not None and CONV_WIN and cout >= 128:
-        ws, m = win[:2]
-        wgm = CONV_WIN if CONV_WIN in (2, 4) else (0 if ws > 64 else 2)
-        if wgm:
-            return "conv_win_planes_kernel<%d,128>" % (64 * wgm)
-    if cout <= 32:
-        return "gather_conv_planes_kernel<128,32,4,1>"
-    if cout <= 64:
-        return "gather_conv_planes_kernel<128,64,4,2>"
-    waves8 = _PLANES_WAVES == 8 or (_PLANES_WAVES == 0 and k1)
-    return "gather_conv_planes_kernel<128,128,%s>" % ("4,2" if waves8 else "2,2")
-
-
-def _win_key(d, hs, ws, cs):
-    """(W, M) when the window kernel covers the layer: 3x3, stride 1, 'same', 16-channel blocks"""
-    if d.kh == 3 and d.kw == 3 and d.sh == 1 and d.sw == 1 and d.pad_t == 1 and d.pad_l == 1 and cs % 16 == 0 \
-            and d.H == d.Ho and d.W == d.Wo:
-        return (ws, d.N * hs * ws, hs, d.N)
-    return None
-
-
-def _gather_variant(cout, flat, m=None):
-    """mirrors dispatch_gather() in csrc/conv.hip (names used by bench.py's roofline report)"""
-    bn = 32 if cout <= 32 else (64 if cout <= 64 else 128)
-    bm = 128
-    if bn == 128 and not flat and m is not None and ((m + 127) // 128) * ((cout + 127) // 128) <= 512:
-        bm = 64
-    if CONV_MODE == "split" and not flat and cout > 32:
-        waves = {(128, 64): "2,2", (64, 128): "1,4", (128, 128): "4,2"}[(bm, bn)]
-        return f"gather_conv_split_kernel<{bm},{bn},{waves}>"
-    return f"gather_conv_kernel<{bm},{bn}{',flat' if flat else ''}>"
 
 
 OPT_CONV_WIN = 0   # include/yolo_hip.h YOLO_OPT_CONV_WIN
@@ -279,17 +206,12 @@ def concurrent_stream(role, beside=None, device=None):
 
 def set_option(key, value):
     """yolo_set_option: run-time kernel-variant switches of the library (benchmarks, tests)"""
-    global WGRAD_WIN
     check(_lib.load().yolo_set_option(int(key), int(value)), "yolo_set_option")
-    if int(key) == OPT_WGRAD_WIN:     # (the kernel names the timer / roofline report use follow the option)
-        WGRAD_WIN = int(value)
 
 
 def reset_options():
     """every option back to its default (the YOLO_* environment variables)"""
-    global WGRAD_WIN
     check(_lib.load().yolo_set_option(-1, 0), "yolo_set_option")
-    WGRAD_WIN = int(_os.environ.get("YOLO_WGRAD_WIN", "1"))
 
 
 def _stream():
@@ -349,12 +271,7 @@ def conv2d_fwd(d, x, w, bias=None, out=None, stats=None, absmax=None):
         check(_lib.load().yolo_conv2d_fwd_absmax(byref(d), _p(x), _p(w), _p(bias), _p(out), _p(stats), _p(absmax),
                                                  _stream()), "yolo_conv2d_fwd")
     if TIMER is not None:
-        # (csrc/stem.hip: stem_fwd_supported -- the direct Cin = 3 kernel takes the first layer at training sizes)
-        stem = (CONV_MODE == "split" and _os.environ.get("YOLO_STEM_DIRECT", "1") != "0" and d.Cin == 3 and d.Cout == 32
-                and d.kh == 3 and d.kw == 3 and d.sh == 1 and d.sw == 1 and d.Ho == d.H and d.Wo == d.W
-                and d.N * d.H * d.W >= (1 << 20))
-        name = "stem_conv3x3_kernel" if stem else _gather_variant(d.Cout, d.Cin % 32 != 0, d.N * d.Ho * d.Wo)
-        TIMER.bracket(name, _conv_flops(d), 1, run)
+        TIMER.bracket(_conv_flops(d), run)
     else:
         run()
     return out
@@ -448,8 +365,7 @@ def conv2d_fwd_planes(d, xp, wp, bias=None, out=None, stats=None, absmax=None, p
         check(_lib.load().yolo_conv2d_fwd_planes_ex(byref(d), _p(xp), _p(wp), _p(bias), _p(out), _p(stats), _p(absmax),
                                                     prec, _stream()), "yolo_conv2d_fwd_planes_ex")
     if TIMER is not None:
-        TIMER.bracket(_planes_variant(d.Cout, _win_key(d, d.H, d.W, d.Cin), d.kh * d.kw == 1), _conv_flops(d), 1, run,
-                      _layer_key(d, "fwd"))
+        TIMER.bracket(_conv_flops(d), run, _layer_key(d, "fwd"))
     else:
         run()
     return out
@@ -474,8 +390,7 @@ def conv2d_fwd_planes_epi(d, xp, wp, bias, epilogue, scale, shift, residual=None
                                                         _p(residual), _p(out), _p(absmax), prec, _stream()),
               "yolo_conv2d_fwd_planes_epi_ex")
     if TIMER is not None:
-        TIMER.bracket(_planes_variant(d.Cout, _win_key(d, d.H, d.W, d.Cin), d.kh * d.kw == 1), _conv_flops(d), 1, run,
-                      _layer_key(d, "fwd"))
+        TIMER.bracket(_conv_flops(d), run, _layer_key(d, "fwd"))
     else:
         run()
     return out
@@ -678,8 +593,7 @@ def conv2d_dgrad_planes(d, dyp, wTp, dx=None, accumulate=False, bnred=None):
               "yolo_conv2d_dgrad_planes_bnred")
         b.nslots = n.value
     if TIMER is not None:
-        TIMER.bracket(_planes_variant(d.Cin, _win_key(d, d.Ho, d.Wo, d.Cout), d.kh * d.kw == 1 and d.sh * d.sw == 1), _conv_flops(d), 1, run,
-                      _layer_key(d, "dgrad"))
+        TIMER.bracket(_conv_flops(d), run, _layer_key(d, "dgrad"))
     else:
         run()
     return dx
@@ -696,8 +610,7 @@ def conv2d_wgrad_planes(d, xp, dyp, dw, dy=None, dbias=None):
         check(_lib.load().yolo_conv2d_wgrad_planes(byref(d), _p(xp), _p(dyp), _p(dw), _stream()),
               "yolo_conv2d_wgrad_planes")
     if TIMER is not None:
-        TIMER.bracket(_wgrad_planes_variant(d.Cout, d.kh * d.kw * d.Cin, d.kh * d.kw, d.N * d.Ho * d.Wo, d), _conv_flops(d), 1, run,
-                      _layer_key(d, "wgrad"))
+        TIMER.bracket(_conv_flops(d), run, _layer_key(d, "wgrad"))
     else:
         run()
     if dbias is not None:
@@ -736,7 +649,7 @@ def conv2d_dgrad(d, dy, wT, dx=None, accumulate=False):
         check(_lib.load().yolo_conv2d_dgrad(byref(d), _p(dy), _p(wT), _p(dx), int(bool(accumulate)), _stream()),
               "yolo_conv2d_dgrad")
     if TIMER is not None:
-        TIMER.bracket(_gather_variant(d.Cin, d.Cout % 32 != 0, d.N * (-(-d.H // d.sh)) * (-(-d.W // d.sw))), _conv_flops(d), d.sh * d.sw, run)
+        TIMER.bracket(_conv_flops(d), run)
     else:
         run()
     return dx
@@ -749,14 +662,7 @@ def conv2d_wgrad(d, x, dy, dw, dbias=None):
     def run():
         check(_lib.load().yolo_conv2d_wgrad(byref(d), _p(x), _p(dy), _p(dw), None, _stream()), "yolo_conv2d_wgrad")
     if TIMER is not None:
-        split = (CONV_MODE == "split" and d.Cout % 4 == 0 and d.Cin % 4 == 0 and d.Cout >= 64
-                 and d.kh * d.kw * d.Cin >= 64)
-        if split:  # mirrors launch_wgrad_split() in csrc/conv_wgrad_split.hip
-            cols = d.kh * d.kw * d.Cin
-            name = "wgrad_split_kernel<%d,%d,2,2>" % (64 if d.Cout <= 64 else 128, 64 if cols <= 64 else 128)
-        else:
-            name = "wgrad_kernel"
-        TIMER.bracket(name, _conv_flops(d), 1, run)
+        TIMER.bracket(_conv_flops(d), run)
     else:
         run()
     if dbias is not None:
@@ -920,7 +826,7 @@ def stem_bn_bwd_wgrad(d, image, y, dout, scale, shift, save_mean, save_invstd, a
                                          _p(save_invstd), act, _p(red), _p(dgamma), _p(dbeta), _p(dw), _p(_STEM_SCRATCH),
                                          _STEM_SCRATCH.numel(), _stream()), "yolo_stem_bn_bwd_wgrad")
     if TIMER is not None:
-        TIMER.bracket("stem_bn_bwd_wgrad_kernel", _conv_flops(d), 1, run)
+        TIMER.bracket(_conv_flops(d), run)
     else:
         run()
 
