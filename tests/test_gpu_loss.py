@@ -60,8 +60,11 @@ def check(loss_fn, cfg, yt, yp):
     ref = loss_fn(torch.tensor(yt, dtype=torch.float64), ypt)
     ref.backward()
     out, dp = run_gpu(cfg, yt, yp)
-    assert abs(out[0] - ref.item()) <= TOL * max(abs(ref.item()), 1.0), (out[0], ref.item())
     gscale = ypt.grad.abs().max().item()
+    print(f"LOSS_CHECK v{cfg.version} {cfg.N}x{cfg.gh}x{cfg.gw} C={cfg.C}: loss error "
+          f"{abs(out[0] - ref.item()) / max(abs(ref.item()), 1.0):.2e}, gradient error "
+          f"{(dp - ypt.grad).abs().max().item() / gscale:.2e} of its largest element")
+    assert abs(out[0] - ref.item()) <= TOL * max(abs(ref.item()), 1.0), (out[0], ref.item())
     assert (dp - ypt.grad).abs().max().item() <= TOL * gscale, ((dp - ypt.grad).abs().max().item(), gscale)
 
 
@@ -246,3 +249,140 @@ def test_loss_cell_ahead_loader_equals_chunk_ahead_loader(version, A, C, g, N):
         assert torch.equal(res[0][1], res[8][1])
     assert torch.equal(res[0][2], res[8][2]) and int(res[0][2].min()) >= 0
     assert np.allclose(res[0][0], res[8][0], rtol=1e-7 if version == 4 else 1e-12, atol=0)
+
+
+# ---- several cells per wave (tests/past_cap_cases.py) ------------------------------------------------------------------
+# Both launchers cap their grid at 2048 workgroups of four waves and a wave walks its cells with `cell += nwaves`: up to
+# 8192 cells every wave has one cell, and the hand-over of the cell-ahead loader (pn / tkn / tbn / pbn -> pc / tkc / tbc /
+# Pb, then prefetch(cell + nwaves)) never runs. The cases below put two to three cells on a wave (the last pass partial)
+# and compare value, parts, gradient and the exported decisions with the fp64 oracle. That the decisions of these inputs do
+# not hang on the precision of the IoU is asserted, for every cell, by tests/test_past_cap_cases_cpu.py.
+import past_cap_cases as PC  # noqa: E402
+
+PC_LW4, PC_LW3, PC_BW = [1.5, 1.2, 5, 0.8], [1.5, 5, 0.8], 0.7
+
+
+def _pc_fn_cfg(case, parts=False):
+    from tf2_yolo_amd import ops
+    g, A, C, v = case.g, case.A, case.C, case.version
+    if v == 3:
+        fn = OL.wrap_yolo_loss_v3(g, A, C, anchors=case.anchors, binary_weight=PC_BW, loss_weight=PC_LW4, ignore_thresh=.6,
+                                  parts=parts)
+    elif v == 2:
+        fn = OL.wrap_yolo_loss_v2(g, A, C, case.anchors, binary_weight=PC_BW, loss_weight=PC_LW4, ignore_thresh=.6)
+    elif v == 4:
+        fn = OL.wrap_yolo_loss_v4(g, A, C, case.anchors, binary_weight=PC_BW, loss_weight=PC_LW3, wh_reg_weight=0.01,
+                                  ignore_thresh=.6, **case.kw)
+    else:
+        fn = OL.wrap_yolo_loss_v1(g, A, C, binary_weight=PC_BW, loss_weight=PC_LW4)
+    cfg = ops.make_loss_cfg(v, case.N, g[0], g[1], A, C, case.anchors, binary_weight=PC_BW,
+                            loss_weight=PC_LW3 if v == 4 else PC_LW4, ignore_thresh=.6, wh_reg_weight=0.01, **case.kw)
+    return fn, cfg
+
+
+def _pc_check_decisions_and_parts(case, cfg, yt, yp):
+    """one more run with decisions=: the exported decisions against those of the fp64 IoUs in EVERY cell, the part sums
+    of loss_out[1:] against the oracle's where it offers them (v3)"""
+    from tf2_yolo_amd import ops
+    cells = PC.loss_cells(case)
+    dec = torch.full((cells, 2), -7, dtype=torch.int32, device="cuda")
+    out, _ = ops.loss_fwd_bwd(cfg, torch.tensor(yt).cuda(), torch.tensor(yp).cuda(), decisions=dec)
+    torch.cuda.synchronize()
+    iou, _ = PC.loss_case_ious(case, torch.float64)
+    want = PC.decisions_of(iou, 0.6, case.kw.get("truth_thresh", 1.0))
+    got = dec.cpu().long()
+    bad = (got != want).any(1).nonzero().reshape(-1)
+    nwaves = min((cells + PC.LOSS_WAVES - 1) // PC.LOSS_WAVES, PC.LOSS_WORKGROUPS) * PC.LOSS_WAVES
+    assert bad.numel() == 0, (f"{bad.numel()} of {cells} cells decided differently; first: cell {int(bad[0])}, pass "
+                              f"{int(bad[0]) // nwaves} of its wave, device {got[bad[0]].tolist()}, oracle "
+                              f"{want[bad[0]].tolist()}, oracle IoUs {iou[bad[0]].tolist()}")
+    if case.version == 3:
+        fn, _ = _pc_fn_cfg(case, parts=True)
+        _, parts = fn(torch.tensor(yt, dtype=torch.float64), torch.tensor(yp, dtype=torch.float64))
+        o = out.cpu().numpy()
+        for i, k in enumerate(("xy", "wh", "conf_obj", "conf_noobj", "prob", "reg")):
+            r = parts[k].item()
+            assert abs(o[1 + i] - r) <= TOL * max(abs(r), 1.0), (k, o[1 + i], r)
+
+
+@pytest.mark.parametrize("case", PC.LOSS_CASES, ids=lambda c: c.name)
+def test_loss_past_the_grid_cap(case):
+    """two to three cells per wave with the launcher's own choice of loader (cell-ahead up to 256 prediction channels,
+    chunk-ahead for v1 and for C = 91): loss, gradient, parts, decisions against the fp64 oracle"""
+    yt, yp = PC.loss_inputs(case)
+    fn, cfg = _pc_fn_cfg(case)
+    check(fn, cfg, yt, yp)
+    _pc_check_decisions_and_parts(case, cfg, yt, yp)
+
+
+@pytest.mark.parametrize("name", PC.LOSS_CHUNK_AHEAD)
+def test_loss_past_the_grid_cap_chunk_ahead_loader(name):
+    """the same under ops.set_option(8, 8), which keeps the chunk-ahead loader: each loader against the ORACLE (two loaders
+    that agree with each other can both be wrong)"""
+    from tf2_yolo_amd import ops
+    case = PC.LOSS_BY_NAME[name]
+    yt, yp = PC.loss_inputs(case)
+    fn, cfg = _pc_fn_cfg(case)
+    try:
+        ops.set_option(8, 8)
+        check(fn, cfg, yt, yp)
+        _pc_check_decisions_and_parts(case, cfg, yt, yp)
+    finally:
+        ops.reset_options()
+
+
+def test_loss_past_the_grid_cap_grad_scale():
+    """grad_scale = 0.5: dpred is half the oracle's gradient, the loss value does not move"""
+    case = PC.LOSS_BY_NAME[PC.LOSS_GRAD_SCALE]
+    yt, yp = PC.loss_inputs(case)
+    fn, cfg = _pc_fn_cfg(case)
+    ypt = torch.tensor(yp, dtype=torch.float64, requires_grad=True)
+    ref = fn(torch.tensor(yt, dtype=torch.float64), ypt)
+    ref.backward()
+    out1, _ = run_gpu(cfg, yt, yp)
+    out, dp = run_gpu(cfg, yt, yp, grad_scale=0.5)
+    half = 0.5 * ypt.grad
+    assert (dp - half).abs().max().item() <= TOL * half.abs().max().item()
+    assert abs(out[0] - ref.item()) <= TOL * max(abs(ref.item()), 1.0)
+    assert np.allclose(out, out1, rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("name", PC.LOSS_NO_GRAD)
+def test_loss_past_the_grid_cap_without_gradient(name):
+    """want_grad=False: the same loss and parts as the run that writes the gradient, up to the order of the fp64 atomics"""
+    from tf2_yolo_amd import ops
+    case = PC.LOSS_BY_NAME[name]
+    yt, yp = PC.loss_inputs(case)
+    fn, cfg = _pc_fn_cfg(case)
+    ytd, ypd = torch.tensor(yt).cuda(), torch.tensor(yp).cuda()
+    with_grad, dp = ops.loss_fwd_bwd(cfg, ytd, ypd)
+    without, none = ops.loss_fwd_bwd(cfg, ytd, ypd, want_grad=False)
+    torch.cuda.synchronize()
+    assert none is None and dp is not None
+    assert np.allclose(without.cpu().numpy(), with_grad.cpu().numpy(), rtol=1e-7 if case.version == 4 else 1e-12, atol=0)
+    ref = fn(torch.tensor(yt, dtype=torch.float64), torch.tensor(yp, dtype=torch.float64)).item()
+    assert abs(float(without[0]) - ref) <= TOL * max(abs(ref), 1.0)
+
+
+@pytest.mark.parametrize("name", PC.METRICS_CASES)
+def test_metrics_past_the_grid_cap(name):
+    """yolo_metrics with two to three cells per wave, versions 1 to 4, against oracle/metrics.py"""
+    from tf2_yolo_amd import ops
+    case = PC.LOSS_BY_NAME[name]
+    yt, yp = PC.loss_inputs(case)
+    _, cfg = _pc_fn_cfg(case)
+    g, A, C = case.g, case.A, case.C
+    out = ops.metrics(cfg, torch.tensor(yt).cuda(), torch.tensor(yp).cuda(), recall_thresh=0.5).cpu().numpy()
+    t, p = torch.tensor(yt, dtype=torch.float64), torch.tensor(yp, dtype=torch.float64)
+    cells = PC.loss_cells(case)
+    if case.version == 1:
+        ref = [OM.obj_acc_v1(t, p, g, A, C).mean().item(), OM.mean_iou_v1(t, p, g, A, C).item(),
+               OM.class_acc_v1(t, p, g, C).item(), OM.recall_v1(t, p, g, A, C, 0.5).item()]
+        got = [out[0] / cells, out[1] / (out[2] + 1e-7), out[3] / (out[2] + 1e-7), out[4] / (out[2] + 1e-7)]
+    else:
+        ref = [OM.obj_acc(t, p, g, A, C).mean().item(), OM.mean_iou(t, p, g, A, C).item(),
+               OM.class_acc(t, p, g, A, C).item(), OM.recall(t, p, g, A, C, 0.5).item()]
+        got = [out[0] / cells, out[1] / (out[2] + 1e-7), out[3] / (out[2] * A + 1e-7), out[4] / (out[2] + 1e-7)]
+    assert out[5] == cells and out[2] == float((t[..., 4] > 0).sum())
+    for a, b in zip(got, ref):
+        assert abs(a - b) < 1e-5, (got, ref)

@@ -225,6 +225,7 @@ __device__ __forceinline__ float loss_channel(const yolo_loss_cfg& c, const int 
       const float pass = (p >= LEPS && p <= ONE_M_EPS) ? 1.f : 0.f;
       const float gm = c.focal_gamma;
       float eo, en, deo, den;  // errors and d(error)/dc
+      float omo, omn;          // 1 - eo, 1 - en
       if (c.label_smooth > 0.f) {
         const float uo = 1.f - c.label_smooth - cc;
         const float un = c.label_smooth - cc;
@@ -232,22 +233,28 @@ __device__ __forceinline__ float loss_channel(const yolo_loss_cfg& c, const int 
         en = fabsf(un);
         deo = (uo > 0.f) ? -1.f : (uo < 0.f ? 1.f : 0.f);
         den = (un > 0.f) ? -1.f : (un < 0.f ? 1.f : 0.f);
+        omo = 1.f - eo;
+        omn = 1.f - en;
       } else {
+        // 1 - (1 - cc) IS cc: formed as written it is cc rounded to 2^-24, 1e-3 of a confidence of 6e-5, and the object
+        // term's gradient ~ 1 / cc misses the fp64 oracle by 1.15e-4 (tests/test_gpu_loss.py: test_loss_past_the_grid_cap[v4])
         eo = 1.f - cc;
         en = cc;
         deo = -1.f;
         den = 1.f;
+        omo = cc;
+        omn = 1.f - cc;
       }
       const bool g2 = gm == 2.f;   // (see the focal branch above)
-      const float ao = g2 ? eo * eo : powf(eo, gm), lo_ = logf(1.f - eo);
-      const float an_ = g2 ? en * en : powf(en, gm), ln_ = logf(1.f - en);
+      const float ao = g2 ? eo * eo : powf(eo, gm), lo_ = logf(omo);
+      const float an_ = g2 ? en * en : powf(en, gm), ln_ = logf(omn);
       const float lo = -obj * ao * lo_;
       const float ln = -noobj * an_ * ln_;
       part[3] += (double)lo;
       part[4] += (double)ln;
       part[0] += (double)c.loss_weight[1] * ((double)lo + (double)c.binary_weight * (double)ln);
-      const float dfo = gm * (g2 ? eo : powf(eo, gm - 1.f)) * lo_ - ao / (1.f - eo);  // d/de [e^g log(1-e)]
-      const float dfn = gm * (g2 ? en : powf(en, gm - 1.f)) * ln_ - an_ / (1.f - en);
+      const float dfo = gm * (g2 ? eo : powf(eo, gm - 1.f)) * lo_ - ao / omo;  // d/de [e^g log(1-e)]
+      const float dfn = gm * (g2 ? en : powf(en, gm - 1.f)) * ln_ - an_ / omn;
       g = c.loss_weight[1] * (-obj * dfo * deo - c.binary_weight * noobj * dfn * den) * pass;
     }
   } else {  // class channel
