@@ -583,6 +583,47 @@ int yolo_metrics(const yolo_loss_cfg* cfg, const float* y_true, const float* y_p
                  float recall_thresh, double* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Classifier top (csrc/classify.hip): GlobalAveragePooling2D + Dense(class_num, softmax) of darknet / darknet53 /
+ * csp_darknet53 (yolov1_5/models/darknet.py:18-19, yolov3/models/darknet.py:38-40, yolov4/models/darknet.py:39-41), the
+ * GlobalAveragePooling2D + Softmax of darknet19 (yolov2/models/darknet.py:24-25), and what Keras' compile strings
+ * "categorical_crossentropy" and "accuracy" compute on them. fp32, no atomics, one fixed summation order per shape: the
+ * results are bit-reproducible.
+ * ------------------------------------------------------------------------------------ */
+/* g[N,C] = mean over H*W of x[N,H,W,C] */
+int yolo_gap_fwd(const float* x, int N, int H, int W, int C, float* g, void* stream);
+/* dx[N,H,W,C] (+)= dg[N,C] / (H*W) */
+int yolo_gap_bwd(const float* dg, int N, int H, int W, int C, float* dx, int accumulate, void* stream);
+/* logits[N,K] = g[N,C] . W[K,C]^T + b[K], p = softmax(logits) with the row maximum subtracted. W = b = NULL: the softmax of
+ * g itself (K == C; logits NULL or g). */
+int yolo_dense_softmax_fwd(const float* g, const float* W, const float* b, int N, int C, int K, float* logits, float* p,
+                           void* stream);
+/* dz = p * (dp - sum_k p_k dp_k) into the workspace dz[N,K]; dg[N,C] = dz . W; dW[K,C] += dz^T . g; db[K] += sum_n dz (dW and
+ * db are slices of the flat gradient buffer: accumulated, as the convolutions' are). W = NULL: dg = dz, no g / dz / dW / db. */
+int yolo_dense_softmax_bwd(const float* dp, const float* p, const float* g, const float* W, int N, int C, int K, float* dz,
+                           float* dg, float* dW, float* db, void* stream);
+/* Keras categorical_crossentropy on probabilities: q = p / sum_k p, qc = clip(q, 1e-7, 1 - 1e-7),
+ * loss_out[0] = mean_n(-sum_k t log qc) (device double[8] like yolo_loss_fwd_bwd's; [1..7] = 0). dpred (optional) = the exact
+ * derivative of that value with respect to p, times grad_scale; the clip passes no gradient outside its range. */
+int yolo_cce_fwd_bwd(const float* t, const float* p, int N, int K, double* loss_out, float* dpred, float grad_scale,
+                     void* stream);
+/* BatchNormalization + activation (linear / LeakyReLU) over ANY channel count, for the class convolution of darknet19
+ * (yolov2/models/darknet.py:23: class_num channels; the yolo_bn_* kernels above take multiples of 4): one workgroup per
+ * channel, meant for the few thousand pixels of a last feature map. y [P,C] is the convolution WITHOUT its bias in training
+ * (mean_offset = the bias, optional: added to the moving mean only) and with it in inference. training != 0: batch
+ * statistics, Keras' moving update (unbiased_moving_var: the batch variance times P / (P - 1)), save_mean / save_invstd; else
+ * the moving statistics. scale, shift [C] are written either way; out = act(fma(scale, y, shift)). */
+int yolo_bn_act_any_fwd(const float* y, long long P, int C, const float* gamma, const float* beta, float* moving_mean,
+                        float* moving_var, const float* mean_offset, float eps, float momentum, int unbiased_moving_var,
+                        int training, int act, float* scale, float* shift, float* save_mean, float* save_invstd, float* out,
+                        void* stream);
+/* its backward: dgamma, dbeta [C] are added to, dy [P,C] is written */
+int yolo_bn_act_any_bwd(const float* y, const float* dout, long long P, int C, const float* gamma, const float* scale,
+                        const float* shift, const float* save_mean, const float* save_invstd, int act, float* dgamma,
+                        float* dbeta, float* dy, void* stream);
+/* out[0] (device double) = mean_n [argmax_k t == argmax_k p], ties to the lowest index (tf.argmax) */
+int yolo_categorical_accuracy(const float* t, const float* p, int N, int K, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Optimizer (Keras Adam defaults: README.md:241; beta1=.9 beta2=.999 eps=1e-7, bias-corrected)
  *   g <- g*grad_scale ; m,v update ; p -= lr_t * m/(sqrt(v)+eps) ; g <- 0 (if zero_grad)
  * ------------------------------------------------------------------------------------ */

@@ -142,6 +142,15 @@ SIGNATURES = {
     "yolo_loss_workspace_bytes": (c_size_t, [POINTER(LossCfg)]),
     "yolo_loss_fwd_bwd": (c_int, [POINTER(LossCfg), _P, _P, _P, _P, c_float, _P, c_size_t, _P]),
     "yolo_metrics": (c_int, [POINTER(LossCfg), _P, _P, c_float, _P, _P]),
+    "yolo_gap_fwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "yolo_gap_bwd": (c_int, [_P, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "yolo_dense_softmax_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "yolo_dense_softmax_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, _P, _P]),
+    "yolo_bn_act_any_fwd": (c_int, [_P, _LL, c_int, _P, _P, _P, _P, _P, c_float, c_float, c_int, c_int, c_int, _P, _P, _P, _P, _P,
+                                    _P]),
+    "yolo_bn_act_any_bwd": (c_int, [_P, _P, _LL, c_int, _P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    "yolo_cce_fwd_bwd": (c_int, [_P, _P, c_int, c_int, _P, _P, c_float, _P]),
+    "yolo_categorical_accuracy": (c_int, [_P, _P, c_int, c_int, _P, _P]),
     "yolo_adam_step": (c_int, [_P, _P, _P, _P, _LL, c_float, c_float, c_float, c_float, c_int, c_float, c_int, _P]),
     "yolo_adam_lr_t": (c_float, [c_float, c_float, c_float, c_int]),
     "yolo_adam_step_dev": (c_int, [_P, _P, _P, _P, _LL, _P, c_int, _P]),

@@ -12,6 +12,11 @@ and `yolo_head(model_body, ...)` appends the fused head units and hands back the
 to a body (`set_weights`, `pretrained_darknet`, a `.npz` path as `pretrained_weights`) are applied when the head
 creates the device buffers. Keras-tensor surgery (layers[i].output, Model(inputs, outputs)) is not available: the
 graphs are fixed by graphs.py, which mirrors the reference's definitions layer for layer.
+
+The backbone classifiers -- `darknet` (yolov1_5/models/darknet.py:13-23), `darknet53` (yolov3/models/darknet.py:19-68),
+`csp_darknet53` (yolov4/models/darknet.py:20-69) -- are executable Models right away: the detector's trunk under the same
+unit names + GlobalAveragePooling2D + Dense(class_num, softmax); `darknet19` (yolov2/models/darknet.py:18-29) ends in a class
+convolution, the pooling and a plain softmax. A trained one is what `pretrained_darknet` takes.
 """
 from . import graphs
 from .model import Model
@@ -98,8 +103,8 @@ def _body(builder_outs, version, pretrained, pretrained_weights, what="pretraine
     body = BodyModel(*builder_outs, version)
     if pretrained is not None:
         if not hasattr(pretrained, "get_layer"):
-            raise ValueError(f"{what} must be a model created by this package (layers are matched by name); the "
-                             "ImageNet classifier variants are outside the HIP path (SURVEY.md section 2 row 16)")
+            raise ValueError(f"{what} must be a model created by this package (layers are matched by name): a detector, "
+                             "or a classifier from darknet / darknet19 / darknet53 / csp_darknet53")
         body._pending.append(("model", pretrained))
     if pretrained_weights is not None:
         if pretrained_weights in ("pascal_voc", "ms_coco", "imagenet"):
@@ -186,7 +191,50 @@ def _keras_tensor_api(name):
 
 
 yolo_keras_app_body = _keras_tensor_api("yolo_keras_app_body")
-darknet53 = _keras_tensor_api("darknet53")
-csp_darknet53 = _keras_tensor_api("csp_darknet53")
-darknet19 = _keras_tensor_api("darknet19")
-darknet = _keras_tensor_api("darknet")
+
+
+# ---- the backbones as classifiers -------------------------------------------------------------------------
+def _classifier(build, include_top, weights, input_shape, class_num, seed, bn_unbiased_moving_var):
+    """trunk + GlobalAveragePooling2D + Dense(class_num, softmax) as an executable Model with one [N, class_num] output
+    (include_top=False: the trunk alone, its feature map as the output). Train it with compile(loss=
+    "categorical_crossentropy", metrics=["accuracy"]) and hand it to yolo_body(pretrained_darknet=...)."""
+    if weights == "imagenet":
+        if include_top:   # the reference's own checks come first (yolov3/models/darknet.py:46-56)
+            if input_shape[0] % 32 > 0 or input_shape[1] % 32 > 0 or input_shape[2] != 3:
+                raise ValueError("When setting `include_top=True` and loading `imagenet` weights, "
+                                 "`input_shape` should be (32x, 32x, 3).")
+            if class_num != 1000:
+                raise ValueError("If using `weights` as `'imagenet'` with `include_top` as true, "
+                                 "`class_num` should be 1000")
+        _offline("weights", weights)
+    m = Model(build(tuple(input_shape), class_num, include_top), version=0, seed=seed,
+              unbiased_moving_var=bn_unbiased_moving_var)
+    if weights is not None:
+        m.load_weights(weights)
+    return m
+
+
+def darknet(input_shape=(224, 224, 3), class_num=10, seed=1234, bn_unbiased_moving_var=True):
+    """DarkNetv1 model (yolov1_5/models/darknet.py:13-23)."""
+    return _classifier(graphs.build_darknet, True, None, input_shape, class_num, seed, bn_unbiased_moving_var)
+
+
+def darknet53(include_top=True, weights="imagenet", input_shape=(448, 448, 3), class_num=1000, seed=1234,
+              bn_unbiased_moving_var=True):
+    """Create Darknet53 model (yolov3/models/darknet.py:19-68). weights: None (random initialization) or the path of a
+    .npz weight file; 'imagenet' needs a download and raises."""
+    return _classifier(graphs.build_darknet53, include_top, weights, input_shape, class_num, seed, bn_unbiased_moving_var)
+
+
+def csp_darknet53(include_top=True, weights="imagenet", input_shape=(448, 448, 3), class_num=1000, seed=1234,
+                  bn_unbiased_moving_var=True):
+    """Create CSPDarknet53 model (yolov4/models/darknet.py:20-69); arguments as darknet53."""
+    return _classifier(graphs.build_csp_darknet53, include_top, weights, input_shape, class_num, seed,
+                       bn_unbiased_moving_var)
+
+
+def darknet19(input_shape=(416, 416, 3), class_num=10, seed=1234, bn_unbiased_moving_var=True):
+    """DarkNet19 model (yolov2/models/darknet.py:18-29): the Darknet-19 trunk, Conv2D_BN_Leaky(class_num, 1),
+    GlobalAveragePooling2D, Softmax. Hand it to yolov2's yolo_body(pretrained_backbone=...)."""
+    return Model(graphs.build_darknet19(tuple(input_shape), class_num), version=0, seed=seed,
+                 unbiased_moving_var=bn_unbiased_moving_var)

@@ -160,7 +160,7 @@ def network_segments(net):
     """(offset, size) of each parameterised unit's slice of the flat buffer, in backward order."""
     segs, units = [], []
     for u in reversed(net.units):
-        if u.kind not in ("conv", "head"):
+        if u.kind not in ("conv", "head", "dense_softmax"):
             continue
         specs = [s for s in (getattr(u, "p_kernel", None), getattr(u, "p_bias", None),
                              getattr(u, "p_gamma", None), getattr(u, "p_beta", None)) if s is not None]

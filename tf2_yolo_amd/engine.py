@@ -105,14 +105,15 @@ def random_normal_002(rng, shape):
 # --------------------------------------------------------------------------------------------
 class TensorRef:
     """Symbolic activation: spatial shape without the batch dimension."""
-    __slots__ = ("tid", "h", "w", "c", "name", "producer")
+    __slots__ = ("tid", "h", "w", "c", "name", "producer", "rank2")
 
-    def __init__(self, tid, h, w, c, name, producer=None):
+    def __init__(self, tid, h, w, c, name, producer=None, rank2=False):
         self.tid, self.h, self.w, self.c, self.name, self.producer = tid, h, w, c, name, producer
+        self.rank2 = rank2     # [N, C]: behind GlobalAveragePooling2D (h = w = 1)
 
     @property
     def shape(self):
-        return (None, self.h, self.w, self.c)
+        return (None, self.c) if self.rank2 else (None, self.h, self.w, self.c)
 
 
 class Unit:
@@ -194,6 +195,43 @@ class SpaceToDepthUnit(Unit):
         self.inputs = [src]
 
 
+class GapUnit(Unit):
+    """GlobalAveragePooling2D: [N,H,W,C] -> [N,C]"""
+    kind = "gap"
+
+    def __init__(self, name, src):
+        super().__init__(name)
+        self.src = src
+        self.inputs = [src]
+
+
+class DenseSoftmaxUnit(Unit):
+    """Dense(K, activation="softmax") on a [N,C] tensor. The kernel is stored [K][C] (the rows the kernels stream); the
+    Keras-facing layout is [C,K]."""
+    kind = "dense_softmax"
+
+    def __init__(self, name, src, K):
+        super().__init__(name)
+        self.src, self.K = src, K
+        self.inputs = [src]
+
+
+class SoftmaxUnit(Unit):
+    """Softmax() on a [N,C] tensor (darknet19's last layer)"""
+    kind = "softmax"
+
+    def __init__(self, name, src):
+        super().__init__(name)
+        self.src = src
+        self.inputs = [src]
+
+
+def he_normal_dense(rng, shape):
+    """Keras he_normal of a Dense kernel stored [K][C]: fan_in = C"""
+    k, c = shape
+    return he_normal_krsc(rng, (k, 1, 1, c)).reshape(k, c)
+
+
 class GraphBuilder:
     """Functional-style builder, one call per reference layer group."""
 
@@ -252,6 +290,31 @@ class GraphBuilder:
         self.outputs.append(out)
         return out
 
+    def gap(self, src, name):
+        out = self._push(GapUnit(name, src), 1, 1, src.c)
+        out.rank2 = True
+        return out
+
+    def dense_softmax(self, src, K, name):
+        if not src.rank2:
+            raise ValueError(f"{name}: Dense takes a [N, C] tensor (put gap() in front)")
+        out = self._push(DenseSoftmaxUnit(name, src, int(K)), 1, 1, int(K))
+        out.rank2 = True
+        return out
+
+    def softmax(self, src, name):
+        if not src.rank2:
+            raise ValueError(f"{name}: Softmax takes a [N, C] tensor (put gap() in front)")
+        out = self._push(SoftmaxUnit(name, src), 1, 1, src.c)
+        out.rank2 = True
+        return out
+
+    def output(self, t):
+        """mark any tensor as a network output (heads register themselves)"""
+        if t not in self.outputs:
+            self.outputs.append(t)
+        return t
+
 
 def count_params(builder):
     """(trainable, non_trainable) parameter counts of a built graph (no device needed)."""
@@ -260,6 +323,8 @@ def count_params(builder):
         if has_filter(u):
             train += u.cout * u.k * u.k * u.src.c + (u.cout if u.bias else 0) + (2 * u.cout if u.bn else 0)
             state += 2 * u.cout if u.bn else 0
+        elif u.kind == "dense_softmax":
+            train += u.K * u.src.c + u.K
     return train, state
 
 
@@ -353,6 +418,9 @@ class Network:
             elif u.kind == "head":
                 u.p_kernel = self.params.add(f"{u.name}/kernel", (u.cout, 1, 1, u.src.c), u.kernel_init)
                 u.p_bias = self.params.add(f"{u.name}/bias", (u.cout,), init_zeros)
+            elif u.kind == "dense_softmax":
+                u.p_kernel = self.params.add(f"{u.name}/kernel", (u.K, u.src.c), he_normal_dense)
+                u.p_bias = self.params.add(f"{u.name}/bias", (u.K,), init_zeros)
 
     def _init_anchors(self):
         """head anchors (v2-v4): views into ONE flat buffer with a gradient twin, so that trainable anchors
@@ -448,6 +516,15 @@ class Network:
                 u.t = new(u)
                 u.yact = new(u)
                 self.act[u.out.tid] = u.yact
+            elif u.kind in ("gap", "dense_softmax", "softmax"):
+                # [N, C] tensors; dsrc = the gradient this unit writes for its input (None: the input needs none)
+                u.buf = torch.empty((N, u.out.c), device=self.device, dtype=torch.float32)
+                src_shape = (N, u.src.h, u.src.w, u.src.c) if u.kind == "gap" else (N, u.src.c)
+                u.dsrc = (torch.empty(src_shape, device=self.device, dtype=torch.float32)
+                          if self._needs_grad[u.src.tid] else None)
+                if u.kind == "dense_softmax":
+                    u.logits, u.dz = torch.empty_like(u.buf), torch.empty_like(u.buf)   # pre-softmax values, their gradient
+                self.act[u.out.tid] = u.buf
             else:
                 u.buf = new(u)
                 if u.kind == "maxpool":
@@ -697,6 +774,16 @@ class Network:
                 raise YoloHipError("residual without BN is not used by any reference graph")
             return
         scale, shift, smean, sinv, stats, _ = self._bn_bufs(u)
+        if u.cout % 4:
+            # a channel count the BatchNorm kernels do not walk (darknet19's class convolution): the exact fp32 convolution and
+            # the one-workgroup-per-channel BatchNorm of csrc/classify.hip, with the same convention for the bias as below
+            if u.residual is not None:
+                raise YoloHipError(f"{u.name}: a residual Add needs a channel count that is a multiple of 4")
+            self._conv_fwd(u, None if training else bias, u.y)
+            ops.bn_act_any_fwd(u.y, u.cout, self.params.view(u.p_gamma.name), self.params.view(u.p_beta.name),
+                               self.state.view(u.s_mean.name), self.state.view(u.s_var.name), scale, shift, smean, sinv, u.act,
+                               u.a, training, mean_offset=bias, unbiased=self.unbiased_moving_var)
+            return
         if training:
             # a conv bias in front of BatchNormalization (YOLOv1.5 / v2) cancels in (y - mean): the convolution
             # runs WITHOUT it -- u.y, the statistics and the saved mean are those of the bias-free tensor, so a
@@ -808,6 +895,13 @@ class Network:
 
     def _fwd_space_to_depth(self, u, training):
         ops.space_to_depth2_fwd(self.act[u.src.tid], u.buf, u.out.c, 0)
+
+    def _fwd_gap(self, u, training):
+        ops.gap_fwd(self.act[u.src.tid], out=u.buf)   # (the fp32 form of its input: plan._plan_fp32_copies)
+
+    def _fwd_dense_softmax(self, u, training):
+        ops.dense_softmax_fwd(self.act[u.src.tid], self.params.view(u.p_kernel.name), self.params.view(u.p_bias.name),
+                              logits=u.logits, p=u.buf)
 
     def _stem_infer_unit(self, u, bias, scale, shift):
         """The RGB stem's inference unit in one launch (yolo_stem_fwd_infer_unit): direct fp32 convolution, folded
@@ -938,11 +1032,16 @@ class Network:
             if isinstance(dout, ops.ChannelSlice) and not self._takes_grad_slice(u):
                 dout = dout.dense((self.batch, u.out.h, u.out.w, u.out.c))
             getattr(self, "_bwd_" + u.kind)(u, dout, grads)
-            if self.grad_ready_hook is not None and has_filter(u):
+            if self.grad_ready_hook is not None and plan.has_params(u):
                 tape.host_call(lambda u=u: self.grad_ready_hook(u))
         self._join_wgrad()
 
     def _bwd_conv(self, u, dout, grads):
+        if u.bn and u.cout % 4:   # (see _fwd_conv)
+            scale, shift, smean, sinv, _, _ = self._bn_bufs(u)
+            dy = ops.bn_act_any_bwd(u.y, dout, u.cout, self.params.view(u.p_gamma.name), scale, shift, smean, sinv, u.act,
+                                    self._gview(u.p_gamma), self._gview(u.p_beta))
+            return self._filter_and_data_grad(u, dy, self._dyp(u, dy), None, grads)
         if u.bn:
             scale, shift, smean, sinv, _, red = self._bn_bufs(u)
             if u.residual is not None:
@@ -1040,6 +1139,28 @@ class Network:
         else:
             ops.maxpool_bwd(dout, N, u.out.h, u.out.w, u.out.c, u.out.c, 0, u.argmax, cur)
 
+    def _bwd_gap(self, u, dout, grads):
+        if not self._needs_grad[u.src.tid]:
+            return
+        cur = grads.get(u.src.tid)
+        if cur is None:
+            grads[u.src.tid] = ops.gap_bwd(dout, u.dsrc, accumulate=False)
+        else:
+            ops.gap_bwd(dout, cur, accumulate=True)
+
+    def _fwd_softmax(self, u, training):
+        ops.dense_softmax_fwd(self.act[u.src.tid], None, None, p=u.buf)
+
+    def _bwd_softmax(self, u, dout, grads):
+        if self._needs_grad[u.src.tid]:
+            ops.dense_softmax_bwd(dout, u.buf, None, None, u.dsrc)
+            self._add_grad(grads, u.src, u.dsrc)
+
+    def _bwd_dense_softmax(self, u, dout, grads):
+        ops.dense_softmax_bwd(dout, u.buf, self.act[u.src.tid], self.params.view(u.p_kernel.name), u.dsrc,
+                              dw=self._gview(u.p_kernel), db=self._gview(u.p_bias), dz=u.dz)
+        self._add_grad(grads, u.src, u.dsrc)
+
     def _bwd_space_to_depth(self, u, dout, grads):
         if self._needs_grad[u.src.tid]:
             cur, acc = self._grad_into(grads, u.src)
@@ -1126,7 +1247,7 @@ class Network:
                 s = store.specs[name]
                 a = store.view(name).detach().cpu().numpy().reshape(s.shape)
                 if name.endswith("/kernel"):
-                    a = np.transpose(a, (1, 2, 3, 0))  # KRSC -> HWIO
+                    a = np.transpose(a, (1, 2, 3, 0) if a.ndim == 4 else (1, 0))  # KRSC -> HWIO, Dense [K,C] -> [C,K]
                 out[name] = a.copy()
         return out
 
@@ -1141,7 +1262,7 @@ class Network:
                 s = store.specs[name]
                 a = np.asarray(weights[name], dtype=np.float32)
                 if name.endswith("/kernel"):
-                    a = np.transpose(a, (3, 0, 1, 2))  # HWIO -> KRSC
+                    a = np.transpose(a, (3, 0, 1, 2) if a.ndim == 4 else (1, 0))  # HWIO -> KRSC, Dense [C,K] -> [K,C]
                 if tuple(a.shape) != s.shape:
                     raise ValueError(f"{name}: shape {a.shape} != {s.shape}")
                 store.view(name).copy_(torch.from_numpy(np.ascontiguousarray(a)).reshape(-1))

@@ -196,14 +196,12 @@ def build_yolov4(input_shape, class_num, anchors=None):
 # ---------------------------------------------------------------------------------------------
 # YOLOv2 (yolov2/models/backbone.py:42-73, yolov2/models/darknet.py:32-106)
 # ---------------------------------------------------------------------------------------------
-def yolov2_body(input_shape):
-    """yolo_body, backbone "darknet" (yolov2/models/darknet.py:32-65): (builder, [out])."""
-    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
-
+def darknet19_body(b, x):
+    """darknet_body (yolov2/models/backbone.py:42-73). Returns (passthrough = Keras layer index 43, out)."""
     def cbl(x, f, k, name):
         return b.conv(x, f, k, name, bias=True)   # Conv2D(use_bias default True)+BN+Leaky (backbone.py:11-18)
 
-    x = cbl(b.input, 32, 3, "conv1")
+    x = cbl(x, 32, 3, "conv1")
     x = b.maxpool(x, 2, "pool1")
     x = cbl(x, 64, 3, "conv2")
     x = b.maxpool(x, 2, "pool2")
@@ -226,7 +224,17 @@ def yolov2_body(input_shape):
     x = cbl(x, 1024, 3, "conv6_3")
     x = cbl(x, 512, 1, "conv6_4")
     x = cbl(x, 1024, 3, "conv6_5")
-    # yolo_body (darknet.py:32-65)
+    return passthrough, x
+
+
+def yolov2_body(input_shape):
+    """yolo_body, backbone "darknet" (yolov2/models/darknet.py:32-65): (builder, [out])."""
+    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
+
+    def cbl(x, f, k, name):
+        return b.conv(x, f, k, name, bias=True)
+
+    passthrough, x = darknet19_body(b, b.input)
     x = cbl(x, 1024, 3, "conv7_1")
     x = cbl(x, 1024, 3, "conv7_2")
     p = cbl(passthrough, 64, 3, "passthrough_conv")
@@ -245,14 +253,12 @@ def build_yolov2(input_shape, class_num, anchors):
 # ---------------------------------------------------------------------------------------------
 # YOLOv1.5 (yolov1_5/models/backbone.py:18-48, yolov1_5/models/darknet.py:26-55)
 # ---------------------------------------------------------------------------------------------
-def yolov1_5_body(input_shape):
-    """yolo_body (yolov1_5/models/darknet.py:26-34): (builder, [out])."""
-    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
-
+def darknet_v1_body(b, x):
+    """darknet_body (yolov1_5/models/backbone.py:18-48)"""
     def cbl(x, f, k, name, stride=1):
         return b.conv(x, f, k, name, stride=stride, padding="same", bias=True)
 
-    x = cbl(b.input, 64, 7, "conv1", stride=2)
+    x = cbl(x, 64, 7, "conv1", stride=2)
     x = b.maxpool(x, 2, "pool1")
     x = cbl(x, 192, 3, "conv2")
     x = b.maxpool(x, 2, "pool2")
@@ -273,11 +279,54 @@ def yolov1_5_body(input_shape):
     x = cbl(x, 1024, 3, "conv5_5")
     x = cbl(x, 1024, 3, "conv5_6", stride=2)
     x = cbl(x, 1024, 3, "conv6_1")
-    x = cbl(x, 1024, 3, "conv6_2")
-    return b, [x]
+    return cbl(x, 1024, 3, "conv6_2")
+
+
+def yolov1_5_body(input_shape):
+    """yolo_body (yolov1_5/models/darknet.py:26-34), the whole of darknet_body: (builder, [out])."""
+    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
+    return b, [darknet_v1_body(b, b.input)]
 
 
 def build_yolov1_5(input_shape, class_num, bbox_num=2):
     b, (x,) = yolov1_5_body(input_shape)
     b.head(x, bbox_num, class_num, 1, None, "out1", level=0)          # yolo_head, yolov1_5/models/darknet.py:37-55
     return b
+
+
+# ---------------------------------------------------------------------------------------------
+# The backbones as classifiers: trunk + GlobalAveragePooling2D + Dense(class_num, softmax)
+# (yolov1_5/models/darknet.py:13-23, yolov3/models/darknet.py:19-42, yolov4/models/darknet.py:20-43); darknet19 ends in a
+# class convolution, the pooling and a plain softmax (yolov2/models/darknet.py:18-29)
+# ---------------------------------------------------------------------------------------------
+def _dense_top(b, x, class_num, include_top):
+    """the top on the trunk's last tensor (layer names top_gap, top_dense); include_top=False: the feature map is the output"""
+    if include_top:
+        x = b.dense_softmax(b.gap(x, "top_gap"), class_num, "top_dense")
+    b.output(x)
+    return b
+
+
+def build_darknet(input_shape, class_num, include_top=True):
+    """darknet (YOLOv1.5)"""
+    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
+    return _dense_top(b, darknet_v1_body(b, b.input), class_num, include_top)
+
+
+def build_darknet19(input_shape, class_num):
+    """darknet19 (yolov2/models/darknet.py:18-29): Conv2D_BN_Leaky(class_num, 1), GlobalAveragePooling2D, Softmax
+    (layer names top_conv, top_bn, top_gap, top_softmax)"""
+    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
+    x = b.conv(darknet19_body(b, b.input)[1], class_num, 1, "top", bias=True)
+    b.output(b.softmax(b.gap(x, "top_gap"), "top_softmax"))
+    return b
+
+
+def build_darknet53(input_shape, class_num, include_top=True):
+    b = GraphBuilder(input_shape, kernel_init=he_normal_krsc)
+    return _dense_top(b, darknet53_body(b, b.input)[2], class_num, include_top)
+
+
+def build_csp_darknet53(input_shape, class_num, include_top=True):
+    b = GraphBuilder(input_shape, kernel_init=random_normal_002)
+    return _dense_top(b, csp_darknet53_body(b, b.input)[2], class_num, include_top)

@@ -100,6 +100,34 @@ def wrap_yolo_loss_v1(grid_shape, bbox_num, class_num, binary_weight=1, loss_wei
     return YoloLoss(1, grid_shape, bbox_num, class_num, None, binary_weight=binary_weight, loss_weight=loss_weight)
 
 
+# ---- classifier loss / metric (compile(loss="categorical_crossentropy", metrics=["accuracy"])) ---------------------
+class CategoricalCrossentropy:
+    """Keras' categorical_crossentropy on probabilities (the classifiers end in a softmax): one-hot or soft float labels
+    [N, K] against predictions [N, K]; the mean over the batch. Same calling forms as YoloLoss."""
+
+    def __init__(self):
+        self.__name__ = "categorical_crossentropy"
+
+    def fwd_bwd(self, y_true, y_pred, grad_scale=1.0, dpred=None, loss_out=None):
+        return ops.cce_fwd_bwd(_as_f32_cuda(y_true), _as_f32_cuda(y_pred), loss_out=loss_out, dpred=dpred,
+                               grad_scale=grad_scale)
+
+    def __call__(self, y_true, y_pred):
+        out, _ = ops.cce_fwd_bwd(_as_f32_cuda(y_true), _as_f32_cuda(y_pred), want_grad=False)
+        return out[0].float()
+
+
+class CategoricalAccuracy:
+    """Keras' categorical_accuracy, averaged over the batch: argmax of the label row equals argmax of the prediction row
+    (first maximum, as tf.argmax)."""
+
+    def __init__(self):
+        self.__name__ = "categorical_accuracy"
+
+    def __call__(self, y_true, y_pred):
+        return ops.categorical_accuracy(_as_f32_cuda(y_true), _as_f32_cuda(y_pred))[0].float()
+
+
 # ---- metrics -------------------------------------------------------------------------------------
 class YoloMetric:
     """kind in {obj_acc, mean_iou, class_acc, recall}; one kernel pass yields all numerators, the

@@ -41,7 +41,8 @@ class Model:
     def __init__(self, builder, version, seed=1234, unbiased_moving_var=True):
         self.net = Network(builder, seed=seed, unbiased_moving_var=unbiased_moving_var)
         self.version = version
-        self.single_output = len(self.net.outputs) == 1 and version in (1, 2)
+        # version 0: a classifier or a bare trunk (bodies.darknet / darknet53 / csp_darknet53) -- one tensor, as in v1.5 / v2
+        self.single_output = len(self.net.outputs) == 1 and version in (0, 1, 2)
         self.optimizer = None
         self.loss = None
         self.metrics = None
@@ -167,6 +168,18 @@ class Model:
                         np.ascontiguousarray(k)).cuda()
                     net.params.view(u.p_bias.name)[lo:hi] = torch.from_numpy(np.asarray(w[1], dtype=np.float32)).cuda()
                 return LayerView(self, name, get, set_)
+            if u.kind == "dense_softmax" and name == u.name:
+                def get(u=u):
+                    k = net.params.view(u.p_kernel.name).cpu().numpy().reshape(u.p_kernel.shape)
+                    return [k.T.copy(), net.params.view(u.p_bias.name).cpu().numpy().copy()]   # Keras: kernel [C,K], bias
+
+                def set_(w, u=u):
+                    k = np.asarray(w[0], dtype=np.float32)
+                    if k.shape != u.p_kernel.shape[::-1]:
+                        raise ValueError(f"{u.name}: kernel shape {k.shape} != {u.p_kernel.shape[::-1]}")
+                    net.params.view(u.p_kernel.name).copy_(torch.from_numpy(np.ascontiguousarray(k.T)).reshape(-1))
+                    net.params.view(u.p_bias.name).copy_(torch.from_numpy(np.asarray(w[1], dtype=np.float32)))
+                return LayerView(self, name, get, set_)
             if u.kind not in ("conv", "head") and name == u.name:
                 return LayerView(self, name, lambda: [], lambda w: None, trainable=False)
         raise ValueError(f"No such layer: {name}")
@@ -188,8 +201,11 @@ class Model:
 
     def set_body_weights(self, other):
         """`model_body.set_weights(pretrained_body.get_weights())` (yolov3/__init__.py:170-171): copy every
-        non-head layer from another Model of the same body, by layer name."""
+        non-head layer from another Model of the same body, by layer name. `other` may be a classifier (bodies.darknet53
+        and the like): the layers of its top (top_*) stay behind."""
         for n in other.layer_names():
+            if n.startswith("top_"):
+                continue
             if n.startswith("out") and ("_box" in n or n.endswith(("_xywhc_conv", "_prob_conv"))):
                 continue
             w = other.get_layer(n).get_weights()
@@ -282,6 +298,17 @@ class Model:
         self.optimizer = optimizer
         self.optimizer.bind(self.net)
         nout = len(self.net.outputs)
+        from . import losses as loss_mod
+
+        def named(v, table, what):
+            if not isinstance(v, str):
+                return v
+            if v.lower() not in table:
+                raise ValueError(f"compile: unknown {what} {v!r}; the strings understood are {sorted(table)}")
+            return table[v.lower()]()
+        loss_names = {"categorical_crossentropy": loss_mod.CategoricalCrossentropy}
+        metric_names = dict.fromkeys(("accuracy", "acc", "categorical_accuracy"), loss_mod.CategoricalAccuracy)
+        loss = [named(l, loss_names, "loss") for l in loss] if isinstance(loss, (list, tuple)) else named(loss, loss_names, "loss")
         self.loss = list(loss) if isinstance(loss, (list, tuple)) else [loss] * nout
         if len(self.loss) != nout:
             raise ValueError(f"need {nout} losses, got {len(self.loss)}")
@@ -289,7 +316,7 @@ class Model:
             metrics = [[] for _ in range(nout)]
         elif nout == 1 and (not metrics or not isinstance(metrics[0], (list, tuple))):
             metrics = [list(metrics)]
-        self.metrics = [list(m) for m in metrics]
+        self.metrics = [[named(v, metric_names, "metric") for v in m] for m in metrics]
         self._loss_bufs = [torch.zeros(8, device="cuda", dtype=torch.float64) for _ in range(nout)]
         self._dpred = None
         self._drop_step_graphs()

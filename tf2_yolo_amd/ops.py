@@ -1029,6 +1029,141 @@ def metrics(cfg, y_true, y_pred, recall_thresh=0.5, out=None):
     return out
 
 
+# ---- the classifier top (csrc/classify.hip) ------------------------------------------------------------------------------
+def gap_fwd(x, out=None):
+    """GlobalAveragePooling2D: x [N,H,W,C] -> [N,C]"""
+    _chk_f32(x, out)
+    if x.dim() != 4:
+        raise YoloHipError("gap_fwd: x must be [N, H, W, C]")
+    n, h, w, c = x.shape
+    if out is None:
+        out = torch.empty((n, c), device=x.device, dtype=torch.float32)
+    if out.numel() != n * c:
+        raise YoloHipError("gap_fwd: the output must hold N * C floats")
+    check(_lib.load().yolo_gap_fwd(_p(x), n, h, w, c, _p(out), _stream()), "yolo_gap_fwd")
+    return out
+
+
+def gap_bwd(dg, dx, accumulate=False):
+    """dx [N,H,W,C] (+)= dg [N,C] / (H W)"""
+    _chk_f32(dg, dx)
+    if dx.dim() != 4:
+        raise YoloHipError("gap_bwd: dx must be [N, H, W, C]")
+    n, h, w, c = dx.shape
+    if dg.numel() != n * c:
+        raise YoloHipError("gap_bwd: dg must hold N * C floats")
+    check(_lib.load().yolo_gap_bwd(_p(dg), n, h, w, c, _p(dx), int(bool(accumulate)), _stream()), "yolo_gap_bwd")
+    return dx
+
+
+def dense_softmax_fwd(g, w, b, logits=None, p=None):
+    """p = softmax(g w^T + b): g [N,C], w [K,C] (or flat), b [K]; w = b = None: p = softmax(g). Returns (logits, p); without
+    weights the logits are g itself."""
+    _chk_f32(g, w, b, logits, p)
+    if g.dim() != 2 or (w is None) != (b is None):
+        raise YoloHipError("dense_softmax_fwd: g must be [N, C]; kernel and bias come together")
+    n, c = g.shape
+    k = c if w is None else b.numel()
+    if w is not None and w.numel() != k * c:
+        raise YoloHipError(f"dense_softmax_fwd: the kernel must hold K * C = {k * c} floats, got {w.numel()}")
+    if p is None:
+        p = torch.empty((n, k), device=g.device, dtype=torch.float32)
+    if w is None:
+        logits = g
+    elif logits is None:
+        logits = torch.empty((n, k), device=g.device, dtype=torch.float32)
+    if p.numel() != n * k or logits.numel() != n * k:
+        raise YoloHipError("dense_softmax_fwd: logits and p must hold N * K floats")
+    check(_lib.load().yolo_dense_softmax_fwd(_p(g), _p(w), _p(b), n, c, k, _p(None if w is None else logits), _p(p), _stream()),
+          "yolo_dense_softmax_fwd")
+    return logits, p
+
+
+def dense_softmax_bwd(dp, p, g, w, dg, dw=None, db=None, dz=None):
+    """backward of dense_softmax_fwd: dg [N,C] is written, dw [K,C] and db [K] are ADDED to (slices of the flat gradient
+    buffer); dz [N,K] is the workspace that receives the logits' gradient. w = None: dg = dz, nothing else."""
+    _chk_f32(dp, p, g, w, dg, dw, db, dz)
+    if dp.dim() != 2 or p.shape != dp.shape:
+        raise YoloHipError("dense_softmax_bwd: dp and p must be [N, K]")
+    n, k = dp.shape
+    if w is None:
+        if dw is not None or db is not None or dg.numel() != n * k:
+            raise YoloHipError("dense_softmax_bwd: without weights dg is [N, K] and there is no dw / db")
+        c = k
+    else:
+        c = w.numel() // k
+        if g is None or dw is None or db is None:
+            raise YoloHipError("dense_softmax_bwd: the Dense form needs g, dw and db")
+        if dz is None:
+            dz = torch.empty_like(dp)
+        if (w.numel() != k * c or g.numel() != n * c or dg.numel() != n * c or dw.numel() != k * c or db.numel() != k
+                or dz.numel() != n * k):
+            raise YoloHipError("dense_softmax_bwd: tensor sizes do not match N, C, K")
+    check(_lib.load().yolo_dense_softmax_bwd(_p(dp), _p(p), _p(g), _p(w), n, c, k, _p(dz), _p(dg), _p(dw), _p(db), _stream()),
+          "yolo_dense_softmax_bwd")
+    return dg
+
+
+def bn_act_any_fwd(y, C, gamma, beta, moving_mean, moving_var, scale, shift, save_mean, save_invstd, act, out, training,
+                   mean_offset=None, eps=BN_EPS, momentum=BN_MOMENTUM, unbiased=False):
+    """BatchNormalization + activation (linear / LeakyReLU) over any channel count, one workgroup per channel
+    (yolo_bn_act_any_fwd): darknet19's class convolution. Training: batch statistics and the moving update."""
+    _chk_f32(y, gamma, beta, moving_mean, moving_var, scale, shift, save_mean, save_invstd, out, mean_offset)
+    if y.numel() % C or out.numel() != y.numel() or any(t.numel() != C for t in (gamma, beta, moving_mean, moving_var, scale,
+                                                                                 shift, save_mean, save_invstd)):
+        raise YoloHipError("bn_act_any_fwd: tensor sizes do not match C")
+    check(_lib.load().yolo_bn_act_any_fwd(_p(y), y.numel() // C, C, _p(gamma), _p(beta), _p(moving_mean), _p(moving_var),
+                                          _p(mean_offset), eps, momentum, int(unbiased), int(bool(training)), int(act),
+                                          _p(scale), _p(shift), _p(save_mean), _p(save_invstd), _p(out), _stream()),
+          "yolo_bn_act_any_fwd")
+    return out
+
+
+def bn_act_any_bwd(y, dout, C, gamma, scale, shift, save_mean, save_invstd, act, dgamma, dbeta, dy=None):
+    """backward of bn_act_any_fwd(training=True): dgamma / dbeta are added to, dy is returned"""
+    _chk_f32(y, dout, gamma, scale, shift, save_mean, save_invstd, dgamma, dbeta, dy)
+    if dy is None:
+        dy = torch.empty_like(y)
+    if y.numel() % C or dout.numel() != y.numel() or dy.numel() != y.numel() or dgamma.numel() != C or dbeta.numel() != C:
+        raise YoloHipError("bn_act_any_bwd: tensor sizes do not match C")
+    check(_lib.load().yolo_bn_act_any_bwd(_p(y), _p(dout), y.numel() // C, C, _p(gamma), _p(scale), _p(shift), _p(save_mean),
+                                          _p(save_invstd), int(act), _p(dgamma), _p(dbeta), _p(dy), _stream()),
+          "yolo_bn_act_any_bwd")
+    return dy
+
+
+def cce_fwd_bwd(y_true, y_pred, loss_out=None, dpred=None, grad_scale=1.0, want_grad=True):
+    """Keras categorical_crossentropy on probabilities [N,K]: (loss_out float64[8] with the loss in [0], dpred)"""
+    _chk_f32(y_true, y_pred, dpred)
+    if y_pred.dim() != 2 or y_true.numel() != y_pred.numel():
+        raise YoloHipError(f"cce: labels {tuple(y_true.shape)} do not match predictions {tuple(y_pred.shape)} ([N, K])")
+    n, k = y_pred.shape
+    if loss_out is None:
+        loss_out = torch.empty(8, device=y_pred.device, dtype=torch.float64)
+    if loss_out.dtype != torch.float64 or loss_out.numel() < 8:
+        raise YoloHipError("cce: loss_out must be float64[8]")
+    if want_grad and dpred is None:
+        dpred = torch.empty_like(y_pred)
+    if want_grad and dpred.numel() != n * k:
+        raise YoloHipError("cce: dpred must hold N * K floats")
+    check(_lib.load().yolo_cce_fwd_bwd(_p(y_true), _p(y_pred), n, k, _p(loss_out), _p(dpred if want_grad else None),
+                                       float(grad_scale), _stream()), "yolo_cce_fwd_bwd")
+    return loss_out, dpred
+
+
+def categorical_accuracy(y_true, y_pred, out=None):
+    """mean_n [argmax t == argmax p] as a device float64[1]"""
+    _chk_f32(y_true, y_pred)
+    if y_pred.dim() != 2 or y_true.numel() != y_pred.numel():
+        raise YoloHipError(f"accuracy: labels {tuple(y_true.shape)} do not match predictions {tuple(y_pred.shape)} ([N, K])")
+    n, k = y_pred.shape
+    if out is None:
+        out = torch.empty(1, device=y_pred.device, dtype=torch.float64)
+    check(_lib.load().yolo_categorical_accuracy(_p(y_true), _p(y_pred), n, k, _p(out), _stream()),
+          "yolo_categorical_accuracy")
+    return out
+
+
 def encode_labels(boxes, cls, first, n_images, img_hw, grid_shape, class_num):
     """yolo_encode_labels: boxes float64 [nb,4] (x1,y1,x2,y2 pixels), cls int32 [nb], first int32 [N+1] (CUDA tensors).
     Returns (label64 [N,gh,gw,5+C] float64, label32 float32)."""

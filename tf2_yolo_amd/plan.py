@@ -90,6 +90,11 @@ def has_filter(u):
     return u.kind in ("conv", "head")
 
 
+def has_params(u):
+    """units that own a slice of the flat parameter / gradient buffers"""
+    return u.kind in ("conv", "head", "dense_softmax")
+
+
 def reads_as_planes(c, t):
     """consumer c takes tensor t as the planes operand of its forward convolution and of its filter gradient, and in no
     other way: it never reads an fp32 copy of t"""
@@ -109,7 +114,7 @@ def plan_graph(units, tensors, input, outputs, opts):
     # consumers per tensor decide whether a tensor needs a gradient at all
     g.needs_grad = {input.tid: False}
     for u in units:
-        g.needs_grad[u.out.tid] = has_filter(u) or any(g.needs_grad[t.tid] for t in u.inputs)
+        g.needs_grad[u.out.tid] = has_params(u) or any(g.needs_grad[t.tid] for t in u.inputs)
     g.consumers, g.n_consumers = {}, {}
     for u in units:
         for t in u.inputs:
