@@ -741,14 +741,19 @@ int yolo_match_detections(const double* gt_rows, int ngt, const double* det_rows
                           unsigned char* gt_flags, long long* class_counts, void* stream);
 
 /* rank[i] = number of rows of the same segment that sort before row i when keys are ordered descending
- * (np.argsort(key)[::-1]; equal keys: the later row first). segment may be NULL (one segment). */
+ * (np.argsort(key)[::-1]). The order is total, so the ranks of a segment of m rows are a permutation of 0 .. m-1 for
+ * any keys: a NaN key orders as +inf (np.argsort puts NaN last, so argsort()[::-1] visits it first), and equal order
+ * keys -- equal values, -0.0 and 0.0, two NaNs, NaN and +inf -- put the later row first. segment may be NULL (one
+ * segment). */
 int yolo_rank_desc(const double* key, const int* segment, int n, int* rank, void* stream);
 
 /* Precision / recall curve of ONE class (measurement.py:299-323): detections (joint confidence, id of the
  * best ground truth, matched flag) are sorted by confidence; point i (0 <= i < n) is computed from the i+1
  * best detections: num_tpp = #matched, num_tp = #distinct matched ground truths, precision = num_tpp/(i+1)
  * (mode 0), num_tp/(num_tp + i+1 - num_tpp) (mode 1), num_tp/(i+1) (mode 2), recall = num_tp/num_gts;
- * point n = (0, last recall). precision and recall hold n+1 doubles. Needs n > 0 and num_gts > 0. */
+ * point n = (0, last recall). precision and recall hold n+1 doubles. Needs n > 0 and num_gts > 0.
+ * The sort is yolo_rank_desc's total order: a NaN confidence orders as +inf (it is visited first), equal
+ * confidences put the later detection first. Every output value is defined whatever the confidences are. */
 size_t yolo_pr_curve_workspace_bytes(int n, int num_gts);
 int yolo_pr_curve(const double* joint, const int* gt_id, const unsigned char* matched, int n, int num_gts,
                   int precision_mode, void* workspace, size_t workspace_bytes, double* precision,

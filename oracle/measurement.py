@@ -62,9 +62,34 @@ def score_table(counts, precision_mode=2):
     return precision, recall, f1
 
 
-def pr_curves(y_trues, y_preds, class_num, conf_threshold=0.05, nms_mode=1, nms_threshold=0.5, nms_sigma=0.5,
-              iou_threshold=0.5, precision_mode=2, max_per_img=100, version=3):
-    """measurement.py:209-323 -> (precisions, recalls): per class arrays of n+1 points"""
+def curve_from_records(rec, num_gts, precision_mode=2, order=None):
+    """measurement.py:299-323, one class: rec [n,3] = (joint confidence, ground-truth id, hit) -> (precision, recall)
+    arrays of n+1 points. order: the visiting order of the rows (indices); None = the reference's
+    np.argsort(joint)[::-1], which leaves exact ties to NumPy's unstable sort."""
+    rec = rec[np.argsort(rec[:, 0])[::-1] if order is None else order]
+    n = len(rec)
+    hit = rec[:, 2].astype(bool)
+    ps, rs = np.zeros(n + 1), np.zeros(n + 1)
+    seen_ids, tpp = set(), 0
+    for k in range(n):   # prefix statistics; the reference recomputes them from scratch for every k
+        if hit[k]:
+            tpp += 1
+            seen_ids.add(rec[k, 1])
+        tp, nd = len(seen_ids), k + 1
+        ps[k] = (tpp / nd) if precision_mode == 0 else (tp / (tp + nd - tpp)) if precision_mode == 1 else (tp / nd)
+        rs[k] = tp / num_gts
+    rs[n] = rs[n - 1] if n else (0.0 if num_gts else np.nan)
+    return ps, rs
+
+
+def class_records(y_trues, y_preds, class_num, conf_threshold=0.05, nms_mode=1, nms_threshold=0.5, nms_sigma=0.5,
+                  iou_threshold=0.5, max_per_img=100, version=3, order=None):
+    """measurement.py:209-297 -> (records, gts): per class the [n,3] rows (joint confidence, ground-truth id, hit) of all
+    images after the per-image cut, and the number of ground truths.
+    order: None = the reference's np.argsort(joint)[::-1]. A callable joint -> visiting order gives tied (or NaN)
+    confidences a defined order: the per-image cut then keeps the first max_per_img rows of that order IN THEIR ORIGINAL
+    ROW ORDER, so that "the later detection" means the same row in the cut and on the curve (without ties the
+    arrangement of the kept rows cannot change the curve)."""
     gts = [0] * class_num
     dets = [np.empty((0, 3)) for _ in range(class_num)]
     for i in range(len(y_trues)):
@@ -84,23 +109,22 @@ def pr_curves(y_trues, y_preds, class_num, conf_threshold=0.05, nms_mode=1, nms_
             else:
                 rec = np.stack((joint, np.zeros(len(d)), np.zeros(len(d))), axis=1)
             if max_per_img is not None and len(rec) > max_per_img:
-                rec = rec[np.argsort(rec[:, 0])[::-1]][:max_per_img]
+                if order is None:
+                    rec = rec[np.argsort(rec[:, 0])[::-1]][:max_per_img]
+                else:
+                    rec = rec[np.sort(order(rec[:, 0])[:max_per_img])]
             dets[c] = np.vstack((dets[c], rec))
+    return dets, gts
+
+
+def pr_curves(y_trues, y_preds, class_num, conf_threshold=0.05, nms_mode=1, nms_threshold=0.5, nms_sigma=0.5,
+              iou_threshold=0.5, precision_mode=2, max_per_img=100, version=3, order=None):
+    """measurement.py:209-323 -> (precisions, recalls): per class arrays of n+1 points (order: see class_records)"""
+    dets, gts = class_records(y_trues, y_preds, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma,
+                              iou_threshold, max_per_img, version, order)
     precisions, recalls = [], []
     for c in range(class_num):
-        rec = dets[c][np.argsort(dets[c][:, 0])[::-1]]
-        n = len(rec)
-        hit = rec[:, 2].astype(bool)
-        ps, rs = np.zeros(n + 1), np.zeros(n + 1)
-        seen_ids, tpp = set(), 0
-        for k in range(n):   # prefix statistics; the reference recomputes them from scratch for every k
-            if hit[k]:
-                tpp += 1
-                seen_ids.add(rec[k, 1])
-            tp, nd = len(seen_ids), k + 1
-            ps[k] = (tpp / nd) if precision_mode == 0 else (tp / (tp + nd - tpp)) if precision_mode == 1 else (tp / nd)
-            rs[k] = tp / gts[c]
-        rs[n] = rs[n - 1] if n else (0.0 if gts[c] else np.nan)
+        ps, rs = curve_from_records(dets[c], gts[c], precision_mode, None if order is None else order(dets[c][:, 0]))
         precisions.append(ps)
         recalls.append(rs)
     return precisions, recalls

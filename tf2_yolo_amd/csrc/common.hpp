@@ -76,6 +76,13 @@ inline int stream_grid(long long work_items, int block) {
   return (int)g;
 }
 
+// Ordering rows by a score (the NMS visiting order, yolo_rank_desc, yolo_pr_curve) needs a TOTAL order: a NaN score compares
+// false both ways, so a comparison sort that is handed such keys can leave its padding entries among the real rows, and a rank
+// by counting gives every NaN row -- and the best ordinary row -- rank 0. np.argsort puts NaN LAST, so the reference's
+// `argsort()[::-1]` visits NaN rows FIRST: the order key of a NaN score is +inf. Equal order keys (-0.0 and 0.0, two NaNs, NaN
+// and +inf) go by index, the higher one first. The score that is stored and reported stays the row's own.
+__device__ __forceinline__ double desc_order_key(double s) { return s != s ? __builtin_huge_val() : s; }
+
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

@@ -298,13 +298,10 @@ __global__ __launch_bounds__(256) void nms_bucket_kernel(int n, int class_num, N
   }
 }
 
-// The order needs a TOTAL order on the scores: a NaN score compares false both ways, and a comparison sort that is handed
-// such keys can leave its (-inf, -1) padding entries among the real rows (an out-of-bounds row index), a rank by counting
-// colliding positions. np.argsort puts NaN LAST, so the reference's `argsort()[::-1]` (utils/tools.py:717) visits NaN rows
-// FIRST: the key of a NaN score is +inf (ties with other NaN / +inf rows by index like every other tie). The score that is
-// stored and reported stays the row's own.
-__device__ __forceinline__ double nms_order_key(double s) { return s != s ? __builtin_huge_val() : s; }
-
+// The order needs a TOTAL order on the scores: desc_order_key (common.hpp) -- a NaN score orders as +inf, ties by index.
+// Without it the LDS bitonic sort below can leave its (-inf, -1) padding entries among the real rows (an out-of-bounds row
+// index), and the rank by counting gives colliding positions.
+//
 // rank of every row inside its class by (score descending, ties: higher original index first -- np.argsort leaves ties
 // undefined, utils/tools.py:717) = the number of rows of the class that come before it: one thread per bucket slot, the
 // class's slots in tiles of 256 through LDS (a workgroup = 256 consecutive slots = one class, or the few small classes
@@ -321,7 +318,7 @@ __global__ __launch_bounds__(256) void nms_rank_kernel(const double* __restrict_
   const bool live = e < total;
   const int i = live ? ws.bidx[e] : 0;
   const double si_raw = live ? ws.bscore[e] : 0.;
-  const double si = nms_order_key(si_raw);
+  const double si = desc_order_key(si_raw);
   const int ci = live ? ws.cls[i] : 0;
   const int beg = live ? ws.class_off[ci] : 0, end = live ? ws.class_off[ci + 1] : 0;
   if (threadIdx.x == 0) s_lo = beg;
@@ -336,7 +333,7 @@ __global__ __launch_bounds__(256) void nms_rank_kernel(const double* __restrict_
     __syncthreads();
     const int j = j0 + threadIdx.x;
     if (j < hi) {
-      s_sc[threadIdx.x] = nms_order_key(ws.bscore[j]);
+      s_sc[threadIdx.x] = desc_order_key(ws.bscore[j]);
       s_ix[threadIdx.x] = ws.bidx[j];
     }
     __syncthreads();
@@ -377,7 +374,7 @@ __global__ __launch_bounds__(1024) void nms_sort_kernel(const double* __restrict
   int N2 = 64;
   while (N2 < nc) N2 <<= 1;
   for (int t = threadIdx.x; t < N2; t += 1024) {
-    s_sc[t] = t < nc ? nms_order_key(ws.bscore[beg + t]) : -__builtin_huge_val();   // padding sorts behind every row
+    s_sc[t] = t < nc ? desc_order_key(ws.bscore[beg + t]) : -__builtin_huge_val();   // padding sorts behind every row
     s_ix[t] = t < nc ? ws.bidx[beg + t] : -1;
   }
   __syncthreads();

@@ -7,9 +7,13 @@
 //                          (np.argmax: first maximum, index inside the class subset) and IoU >= threshold;
 //                          per class: #detections, #ground truths, #matched detections (TPP), #distinct
 //                          matched ground truths (TP)                               (measurement.py:104-138)
-//   yolo_rank_desc         rank of every row inside its segment by key, descending (np.argsort(...)[::-1];
-//                          ties, which numpy leaves to its unstable sort: the later row first)
-//   yolo_pr_curve          one class: sort detections by joint confidence, then for every prefix the number
+//   yolo_rank_desc         rank of every row inside its segment by key, descending (np.argsort(...)[::-1]). A TOTAL
+//                          order, so that the ranks of a segment are a permutation of 0 .. m-1 whatever the keys:
+//                          the order key of NaN is +inf (desc_order_key, common.hpp: argsort()[::-1] visits NaN
+//                          first); equal order keys -- ties, which numpy leaves to its unstable sort, -0.0 and 0.0,
+//                          two NaNs, NaN and +inf -- put the later row first
+//   yolo_pr_curve          one class: sort detections by joint confidence (the order of yolo_rank_desc: every
+//                          slot of the sorted flags is written exactly once), then for every prefix the number
 //                          of matched detections and of DISTINCT matched ground truths -> precision (3 modes)
 //                          and recall, plus the closing (0, last recall) point      (measurement.py:299-323)
 #include "common.hpp"
@@ -97,12 +101,12 @@ __global__ __launch_bounds__(256) void rank_desc_kernel(const double* __restrict
   __shared__ int s_seg[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
   const bool valid = i < n;
-  const double ki = valid ? key[i] : 0.0;
+  const double ki = valid ? desc_order_key(key[i]) : 0.0;
   const int si = valid ? (seg ? seg[i] : 0) : -2;
   int r = 0;
   for (int base = 0; base < n; base += 256) {
     const int j = base + threadIdx.x;
-    s_key[threadIdx.x] = (j < n) ? key[j] : 0.0;
+    s_key[threadIdx.x] = (j < n) ? desc_order_key(key[j]) : 0.0;   // (a key: no NaN, so == and > below are a total order)
     s_seg[threadIdx.x] = (j < n) ? (seg ? seg[j] : 0) : -3;
     __syncthreads();
     const int lim = (n - base < 256) ? (n - base) : 256;

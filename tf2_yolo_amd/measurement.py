@@ -6,7 +6,10 @@ measure.hip); the precision / recall curve of a class is one more kernel over al
 keeps what the reference keeps in Python lists: which rows belong to which image and class.
 
 Differences, all in corners the reference leaves undefined or broken:
-  * exact ties of the joint confidence: the later detection sorts first (np.argsort is unstable);
+  * exact ties of the joint confidence: the later detection sorts first (np.argsort is unstable), in the per-image
+    `max_per_img` cut and on the curve. "Later" is the row order of decode / NMS inside an image, then the image order.
+    The order is total (measure.hip, yolo_rank_desc): -0.0 and 0.0 tie, and a NaN confidence would order as +inf, i.e.
+    first, like the reference's argsort()[::-1] -- decode never lets one through (`conf * prob >= threshold` is false);
   * a class without any detection: the reference re-uses `num_tp` of the PREVIOUS class (or raises
     NameError for class 0); here its curve is the single point (0, 0) -- (0, nan) if it also has no
     ground truth;

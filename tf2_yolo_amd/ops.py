@@ -1391,7 +1391,7 @@ def match_detections(gt_rows, det_rows, class_num, iou_threshold, class_counts):
 
 
 def rank_desc(key, segment=None):
-    """rank of every element inside its segment, keys descending (ties: later element first)"""
+    """rank of every element inside its segment, keys descending (NaN orders as +inf; ties: later element first)"""
     n = int(key.numel())
     rank = torch.empty(n, device=key.device, dtype=torch.int32)
     if n:
