@@ -712,6 +712,41 @@ int yolo_nms_select(const double* rows, int n, int class_num, int mode, double n
                     double sigma, unsigned char* keep_out, double* rows_out, int* count_out, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Decode + NMS of a whole batch without leaving the device (utils/tools.py:370-438, 687-786 applied to every image).
+ * Decode: `levels` (1..8) tensors preds[l] = device [B, gh[l], gw[l], D] of float32 (is_f64[l] == 0) or float64, in ONE
+ * count -> scan -> write sequence whose grid covers every image. thresholds[l] is compared with the product conf * prob in
+ * the level's own type (for a float32 level pass a value float32 holds exactly). The pointer arrays and gh / gw / A /
+ * is_f64 / thresholds are HOST arrays of `levels` entries.
+ *   yolo_decode_batch_count  img_off (device int [B + 1]) <- the first row of every image, img_off[B] = the row count n;
+ *                            the workspace keeps the block offsets for ...
+ *   yolo_decode_batch_write  (same arguments, same untouched workspace) rows_out [max_rows][7] float64 <- the rows,
+ *                            image-major; inside an image the order of yolo_decode_level called level by level on that
+ *                            image's slices (byte-identical). Rows beyond max_rows are not written. */
+size_t yolo_decode_batch_workspace_bytes(int levels, const int* gh, const int* gw, const int* A, int C, int B);
+int yolo_decode_batch_count(const void* const* preds, const int* is_f64, int levels, int B, const int* gh, const int* gw,
+                            const int* A, int C, int version, const double* thresholds, int* img_off, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int yolo_decode_batch_write(const void* const* preds, const int* is_f64, int levels, int B, const int* gh, const int* gw,
+                            const int* A, int C, int version, const double* thresholds, double* rows_out, int max_rows,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* NMS + gather of a batch's rows (utils/tools.py:687-786 per image): the kernels of yolo_nms_select over B * class_num
+ * segments, segment = image * class_num + class, image of row i from img_off (device int [B + 1], rows image-major as
+ * yolo_decode_batch_write stores them). The bit matrices are sized from the segment counts, not from n:
+ *   yolo_nms_batch_prepare  counts and scans the segments; *mask_words_out (device) <- the 64-bit words the matrices take
+ *   yolo_nms_batch_select   (same rows, n, B, class_num, same untouched workspace) `mask` = device buffer of `mask_words`
+ *                           words (fewer than asked for, or NULL / 0: every segment takes the walk kernels, same
+ *                           results). rows_out [<= n][7] <- the kept rows: image-major, classes ascending inside an
+ *                           image, original order inside a class = the per-image yolo_nms_select outputs concatenated
+ *                           (column 5 is the row's own class); kept_off_out (device int [B + 1]) <- the first kept row
+ *                           of every image, [B] = the number of kept rows. keep_out as yolo_nms.
+ * No launch and no device read per image: the caller reads n, *mask_words_out and kept_off_out. */
+size_t yolo_nms_batch_workspace_bytes(int n, int B, int class_num);
+int yolo_nms_batch_prepare(const double* rows, int n, const int* img_off, int B, int class_num, long long* mask_words_out,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int yolo_nms_batch_select(const double* rows, int n, int B, int class_num, int mode, double nms_threshold,
+                          double conf_threshold, double sigma, void* mask, long long mask_words, unsigned char* keep_out,
+                          double* rows_out, int* kept_off_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* cal_iou as a stand-alone broadcasting kernel -- the reference's two public functions of that name:
  *   utils/tools.py:630-684       cal_iou(xywh_true, xywh_pred, mode): NumPy float64/float32, mode 1 IoU, 2 DIoU
  *   yolov3/losses/loss.py:9-37   cal_iou(xywh_true, xywh_pred, grid_shape): x / grid_w, y / grid_h first (same text

@@ -174,6 +174,15 @@ SIGNATURES = {
     "yolo_pr_curve": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P, _P]),
     "yolo_nms": (c_int, [_P, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, c_size_t, _P]),
     "yolo_nms_select": (c_int, [_P, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P, c_size_t, _P]),
+    "yolo_decode_batch_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int]),
+    "yolo_decode_batch_count": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int, POINTER(c_int), POINTER(c_int),
+                                        POINTER(c_int), c_int, c_int, POINTER(c_double), _P, _P, c_size_t, _P]),
+    "yolo_decode_batch_write": (c_int, [POINTER(c_void_p), POINTER(c_int), c_int, c_int, POINTER(c_int), POINTER(c_int),
+                                        POINTER(c_int), c_int, c_int, POINTER(c_double), _P, c_int, _P, c_size_t, _P]),
+    "yolo_nms_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "yolo_nms_batch_prepare": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
+    "yolo_nms_batch_select": (c_int, [_P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, _P, _LL, _P, _P, _P, _P,
+                                      c_size_t, _P]),
 }
 
 _lib = None
@@ -182,7 +191,7 @@ _lib = None
 _QUERIES = {"yolo_last_error", "yolo_last_conv_kernel", "yolo_abi_version", "yolo_bnred_slots_cap", "yolo_device_available", "yolo_conv_workspace_bytes", "yolo_planes_bytes",
             "yolo_stem_bwd_scratch_bytes", "yolo_loss_workspace_bytes", "yolo_decode_workspace_bytes",
             "yolo_nms_workspace_bytes", "yolo_pr_curve_workspace_bytes", "yolo_wgrad_workspace_bytes", "yolo_adam_lr_t",
-            "yolo_grad_sqnorm_workspace_bytes",
+            "yolo_grad_sqnorm_workspace_bytes", "yolo_decode_batch_workspace_bytes", "yolo_nms_batch_workspace_bytes",
             "yolo_set_option", "yolo_set_debug_buffer", "yolo_set_conv_workspace", "yolo_set_wgrad_workspace"}
 
 

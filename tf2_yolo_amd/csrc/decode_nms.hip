@@ -46,31 +46,83 @@ __device__ __forceinline__ bool decode_flag(const T* pred, const DecodeGeom& g, 
   return true;
 }
 
+// the candidates [base, base + DEC_ITEMS) of one thread: which pass the threshold (product in the input's own type)
 template <typename T>
-__global__ __launch_bounds__(DEC_BLOCK) void decode_count_kernel(const T* __restrict__ pred, DecodeGeom g, T thr,
-                                                                 int* __restrict__ block_counts) {
-  __shared__ int wsum[DEC_BLOCK / 64];
-  const long long base = ((long long)blockIdx.x * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
+__device__ __forceinline__ int decode_thread_flags(const T* __restrict__ pred, const DecodeGeom& g, T thr, long long base,
+                                                   bool (&flag)[DEC_ITEMS]) {
   int cnt = 0;
   for (int it = 0; it < DEC_ITEMS; ++it) {
     const long long e = base + it;
+    flag[it] = false;
     if (e < g.total) {
       int yi, xi, bi, ci;
       long long bo, po;
       decode_flag(pred, g, e, yi, xi, bi, ci, bo, po);
       const T joint = pred[bo + 4] * pred[po];
-      cnt += (joint >= thr) ? 1 : 0;
+      flag[it] = joint >= thr;
     }
+    cnt += flag[it] ? 1 : 0;
   }
+  return cnt;
+}
+
+// sum of cnt over the workgroup (valid in thread 0)
+__device__ __forceinline__ int decode_block_sum(int cnt, int* wsum) {
   int s = cnt;
   for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int t = 0;
+  int t = 0;
+  if (threadIdx.x == 0)
     for (int w = 0; w < DEC_BLOCK / 64; ++w) t += wsum[w];
-    block_counts[blockIdx.x] = t;
+  return t;
+}
+
+// the flagged candidates of one thread as rows, from row block_offset + (flagged candidates of the threads before it)
+template <typename T>
+__device__ __forceinline__ void decode_thread_write(const T* __restrict__ pred, const DecodeGeom& g, long long base,
+                                                    const bool (&flag)[DEC_ITEMS], int cnt, int block_offset, int* wsum,
+                                                    double* __restrict__ rows, int max_rows) {
+  // exclusive prefix over the block's threads (thread order == candidate order)
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = cnt;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
   }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int woff = 0;
+  for (int w = 0; w < wave; ++w) woff += wsum[w];
+  int pos = block_offset + woff + incl - cnt;
+  for (int it = 0; it < DEC_ITEMS; ++it) {
+    if (!flag[it]) continue;
+    if (pos < max_rows) {
+      const long long e = base + it;
+      int yi, xi, bi, ci;
+      long long bo, po;
+      decode_flag(pred, g, e, yi, xi, bi, ci, bo, po);
+      double* r = rows + (long long)pos * 7;
+      r[0] = ((double)xi + (double)pred[bo + 0]) / (double)g.gw;
+      r[1] = ((double)yi + (double)pred[bo + 1]) / (double)g.gh;
+      r[2] = (double)pred[bo + 2];
+      r[3] = (double)pred[bo + 3];
+      r[4] = (double)pred[bo + 4];
+      r[5] = (double)ci;
+      r[6] = (double)pred[po];
+    }
+    ++pos;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(DEC_BLOCK) void decode_count_kernel(const T* __restrict__ pred, DecodeGeom g, T thr,
+                                                                 int* __restrict__ block_counts) {
+  __shared__ int wsum[DEC_BLOCK / 64];
+  const long long base = ((long long)blockIdx.x * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
+  bool flag[DEC_ITEMS];
+  const int t = decode_block_sum(decode_thread_flags(pred, g, thr, base, flag), wsum);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
 }
 
 // single block: exclusive scan of block_counts[nb] in place, offset by *count; *count += total
@@ -106,48 +158,71 @@ __global__ __launch_bounds__(DEC_BLOCK) void decode_write_kernel(const T* __rest
   __shared__ int wsum[DEC_BLOCK / 64];
   const long long base = ((long long)blockIdx.x * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
   bool flag[DEC_ITEMS];
-  int cnt = 0;
-  for (int it = 0; it < DEC_ITEMS; ++it) {
-    const long long e = base + it;
-    flag[it] = false;
-    if (e < g.total) {
-      int yi, xi, bi, ci;
-      long long bo, po;
-      decode_flag(pred, g, e, yi, xi, bi, ci, bo, po);
-      const T joint = pred[bo + 4] * pred[po];
-      flag[it] = joint >= thr;
-    }
-    cnt += flag[it] ? 1 : 0;
-  }
-  // exclusive prefix over the block's threads (thread order == candidate order)
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = cnt;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int woff = 0;
-  for (int w = 0; w < wave; ++w) woff += wsum[w];
-  int pos = block_offsets[blockIdx.x] + woff + incl - cnt;
-  for (int it = 0; it < DEC_ITEMS; ++it) {
-    if (!flag[it]) continue;
-    if (pos < max_rows) {
-      const long long e = base + it;
-      int yi, xi, bi, ci;
-      long long bo, po;
-      decode_flag(pred, g, e, yi, xi, bi, ci, bo, po);
-      double* r = rows + (long long)pos * 7;
-      r[0] = ((double)xi + (double)pred[bo + 0]) / (double)g.gw;
-      r[1] = ((double)yi + (double)pred[bo + 1]) / (double)g.gh;
-      r[2] = (double)pred[bo + 2];
-      r[3] = (double)pred[bo + 3];
-      r[4] = (double)pred[bo + 4];
-      r[5] = (double)ci;
-      r[6] = (double)pred[po];
-    }
-    ++pos;
+  const int cnt = decode_thread_flags(pred, g, thr, base, flag);
+  decode_thread_write(pred, g, base, flag, cnt, block_offsets[blockIdx.x], wsum, rows, max_rows);
+}
+
+// ---- a whole batch: every level's [B, gh, gw, D] tensor in ONE count -> scan -> write sequence ----
+// A workgroup never straddles an image or a level: grid.y is the image, grid.x runs over the levels' workgroups one level
+// after the other (DecodeBatch::blk_off). The counts are stored image-major -- block_counts[image * blocks + blockIdx.x] --
+// so that ONE flat exclusive scan (decode_scan_kernel) puts the rows image-major, levels in argument order inside an image
+// and (y, x, box, class) inside a level: the per-image outputs concatenated. The scanned entry of an image's first workgroup
+// is the image's first row (decode_batch_offsets_kernel).
+constexpr int DEC_MAX_LEVELS = 8;
+struct DecodeBatch {
+  const void* pred[DEC_MAX_LEVELS];
+  DecodeGeom g[DEC_MAX_LEVELS];
+  long long img_stride[DEC_MAX_LEVELS];   // elements of one image: gh * gw * D
+  double thr[DEC_MAX_LEVELS];             // (for a float32 level: a value float32 holds exactly)
+  int f64[DEC_MAX_LEVELS];
+  int blk_off[DEC_MAX_LEVELS + 1];        // first workgroup of a level inside an image; [levels] = workgroups per image
+  int levels;
+};
+
+__device__ __forceinline__ int decode_batch_level(const DecodeBatch& d) {
+  int l = 0;
+  while (l + 1 < d.levels && (int)blockIdx.x >= d.blk_off[l + 1]) ++l;
+  return l;
+}
+
+__global__ __launch_bounds__(DEC_BLOCK) void decode_batch_count_kernel(DecodeBatch d, int* __restrict__ block_counts) {
+  __shared__ int wsum[DEC_BLOCK / 64];
+  const int l = decode_batch_level(d);
+  const DecodeGeom g = d.g[l];
+  const long long base = ((long long)(blockIdx.x - d.blk_off[l]) * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
+  const long long img = (long long)blockIdx.y * d.img_stride[l];
+  bool flag[DEC_ITEMS];
+  int cnt;
+  if (d.f64[l]) cnt = decode_thread_flags(reinterpret_cast<const double*>(d.pred[l]) + img, g, d.thr[l], base, flag);
+  else cnt = decode_thread_flags(reinterpret_cast<const float*>(d.pred[l]) + img, g, (float)d.thr[l], base, flag);
+  const int t = decode_block_sum(cnt, wsum);
+  if (threadIdx.x == 0) block_counts[(long long)blockIdx.y * d.blk_off[d.levels] + blockIdx.x] = t;
+}
+
+__global__ void decode_batch_offsets_kernel(const int* __restrict__ block_offsets, int blocks_per_image, int B,
+                                            const int* __restrict__ count, int* __restrict__ img_off) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) img_off[b] = block_offsets[(long long)b * blocks_per_image];
+  else if (b == B) img_off[B] = *count;
+}
+
+__global__ __launch_bounds__(DEC_BLOCK) void decode_batch_write_kernel(DecodeBatch d, const int* __restrict__ block_offsets,
+                                                                       double* __restrict__ rows, int max_rows) {
+  __shared__ int wsum[DEC_BLOCK / 64];
+  const int l = decode_batch_level(d);
+  const DecodeGeom g = d.g[l];
+  const long long base = ((long long)(blockIdx.x - d.blk_off[l]) * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
+  const long long img = (long long)blockIdx.y * d.img_stride[l];
+  const int boff = block_offsets[(long long)blockIdx.y * d.blk_off[d.levels] + blockIdx.x];
+  bool flag[DEC_ITEMS];
+  if (d.f64[l]) {
+    const double* pred = reinterpret_cast<const double*>(d.pred[l]) + img;
+    const int cnt = decode_thread_flags(pred, g, d.thr[l], base, flag);
+    decode_thread_write(pred, g, base, flag, cnt, boff, wsum, rows, max_rows);
+  } else {
+    const float* pred = reinterpret_cast<const float*>(d.pred[l]) + img;
+    const int cnt = decode_thread_flags(pred, g, (float)d.thr[l], base, flag);
+    decode_thread_write(pred, g, base, flag, cnt, boff, wsum, rows, max_rows);
   }
 }
 
@@ -184,7 +259,8 @@ struct NmsWs {
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-static size_t nms_carve(int n, int class_num, void* base, NmsWs* ws) {
+// with_mask false (the batched path): the matrices live in a buffer of their own, sized from the segment counts
+static size_t nms_carve(int n, int class_num, void* base, NmsWs* ws, bool with_mask = true) {
   size_t off = 0;
   char* b = reinterpret_cast<char*>(base);
   auto take = [&](size_t bytes) {
@@ -209,7 +285,7 @@ static size_t nms_carve(int n, int class_num, void* base, NmsWs* ws) {
   w.tile_off = (int*)take(sizeof(int) * (class_num + 1));
   // sum over the classes of n_c * ceil(n_c / 64) words with every n_c <= NMS_MASK_MAX and sum n_c <= n
   const size_t per_row = (size_t)((n < NMS_MASK_MAX ? n : NMS_MASK_MAX) / 64 + 1);
-  w.mask = (unsigned long long*)take(sizeof(unsigned long long) * per_row * (size_t)n);
+  w.mask = with_mask ? (unsigned long long*)take(sizeof(unsigned long long) * per_row * (size_t)n) : nullptr;
   if (ws) *ws = w;
   return off;
 }
@@ -861,6 +937,138 @@ __global__ __launch_bounds__(256) void nms_gather_kernel(const double* __restric
   for (int k = 0; k < 7; ++k) dst[k] = src[k];
 }
 
+// ---- a whole batch (utils/tools.py:687-786 per image): the same kernels over B * class_num segments ----
+// NMS is per class, so NMS of B images is the pipeline above with the segment key image * class_num + class. Only the
+// prepare kernel looks at a row's class column; everything else works from ws.cls / class_cnt / class_off. The gather emits
+// "segments ascending, original order inside a segment": image-major, classes ascending inside an image -- the per-image
+// outputs concatenated -- and the tie rule holds because the rows are stored image-major in per-image decode order.
+__global__ __launch_bounds__(256) void nms_prepare_batch_kernel(const double* __restrict__ rows, int n,
+                                                                const int* __restrict__ img_off, int B, int class_num,
+                                                                NmsWs ws) {
+  __shared__ int s_cnt[NMS_LDS_CLASSES];
+  const int segs = B * class_num;
+  const bool lds = segs <= NMS_LDS_CLASSES;
+  if (lds)
+    for (int c = threadIdx.x; c < segs; c += 256) s_cnt[c] = 0;
+  __syncthreads();
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) {
+    const double* r = rows + (long long)i * 7;
+    int c = (int)r[5];  // astype("int") truncates toward zero
+    if (c < 0 || c >= class_num) {
+      c = -1;
+    } else {
+      int lo = 0, hi = B - 1;   // the last image whose first row is at or before i (an image without rows has an empty range)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (img_off[mid] <= i) lo = mid; else hi = mid - 1;
+      }
+      c += lo * class_num;
+    }
+    ws.cls[i] = c;
+    ws.score[i] = r[4] * r[6];
+    ws.pos_of[i] = -1;
+    ws.removed[i] = 0;
+    if (c >= 0) {
+      if (lds) atomicAdd(&s_cnt[c], 1);
+      else atomicAdd(&ws.class_cnt[c], 1);
+    }
+  }
+  if (lds) {
+    __syncthreads();
+    for (int c = threadIdx.x; c < segs; c += 256)
+      if (s_cnt[c] != 0) atomicAdd(&ws.class_cnt[c], s_cnt[c]);
+  }
+}
+
+// inclusive prefix sum of v over a workgroup of 1024 threads (16 waves); total = the workgroup's sum. s_w: 16 entries of LDS.
+__device__ __forceinline__ long long nms_block_scan(long long v, long long* s_w, long long& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long incl = v;
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  __syncthreads();   // (the scan before this one has read s_w)
+  if (lane == 63) s_w[wave] = incl;
+  __syncthreads();
+  long long off = 0, tot = 0;
+  for (int w = 0; w < 16; ++w) {
+    const long long x = s_w[w];
+    if (w < wave) off += x;
+    tot += x;
+  }
+  total = tot;
+  return incl + off;
+}
+
+// nms_class_scan_kernel for thousands of segments: one workgroup, 1024 segments per step, carries in registers. Also tells
+// the host how many words the matrices take (*mask_words_out): the batched path sizes them from the segment counts.
+__global__ __launch_bounds__(1024) void nms_seg_scan_kernel(int segs, NmsWs ws, int want_mask,
+                                                            long long* __restrict__ mask_words_out) {
+  __shared__ long long s_w[16];
+  long long acc = 0, tiles = 0, words = 0;
+  for (int base = 0; base < segs; base += 1024) {
+    const int c = base + threadIdx.x;
+    const int nc = c < segs ? ws.class_cnt[c] : 0;
+    const bool has = want_mask && nc > 0 && nc <= NMS_MASK_MAX;
+    const long long T = (nc + 63) >> 6;
+    const long long t = has ? T * (T + 1) / 2 : 0;
+    const long long w = has ? (long long)nc * T : 0;
+    long long tot_n, tot_t, tot_w;
+    const long long in_n = nms_block_scan(nc, s_w, tot_n);
+    const long long in_t = nms_block_scan(t, s_w, tot_t);
+    const long long in_w = nms_block_scan(w, s_w, tot_w);
+    if (c < segs) {
+      ws.class_off[c] = (int)(acc + in_n - nc);
+      ws.tile_off[c] = (int)(tiles + in_t - t);
+      ws.mask_off[c] = has ? words + in_w - w : -1;
+    }
+    acc += tot_n;
+    tiles += tot_t;
+    words += tot_w;
+  }
+  if (threadIdx.x == 0) {
+    ws.class_off[segs] = (int)acc;
+    ws.tile_off[segs] = (int)tiles;
+    ws.mask_off[segs] = words;
+    *mask_words_out = words;
+  }
+}
+
+// The matrices' buffer holds `capacity_words`. If the segments need more (a caller that did not ask, or passed none), no
+// segment gets a matrix: the walk / tiled kernels resolve them all, with the same results.
+__global__ __launch_bounds__(1024) void nms_mask_fit_kernel(int segs, NmsWs ws, long long capacity_words) {
+  const bool over = ws.mask_off[segs] > capacity_words;
+  __syncthreads();   // (every thread has read the total before the first one overwrites it)
+  if (!over) return;
+  for (int c = threadIdx.x; c <= segs; c += 1024) {
+    ws.mask_off[c] = c < segs ? -1 : 0;
+    ws.tile_off[c] = 0;
+  }
+}
+
+// nms_kept_scan_kernel for thousands of segments, plus the per-image table: kept_off[b] = the first output row of image
+// b's first segment, kept_off[B] = the number of kept rows
+__global__ __launch_bounds__(1024) void nms_kept_scan_batch_kernel(int segs, int class_num, NmsWs ws,
+                                                                   int* __restrict__ kept_off) {
+  __shared__ long long s_w[16];
+  long long acc = 0;
+  for (int base = 0; base < segs; base += 1024) {
+    const int c = base + threadIdx.x;
+    const int k = c < segs ? ws.fill[c] : 0;
+    long long tot;
+    const long long incl = nms_block_scan(k, s_w, tot);
+    if (c < segs) {
+      const int first = (int)(acc + incl - k);
+      ws.class_cnt[c] = first;             // (class_cnt is free by now: first output position of the segment)
+      if (c % class_num == 0) kept_off[c / class_num] = first;
+    }
+    acc += tot;
+  }
+  if (threadIdx.x == 0) kept_off[segs / class_num] = (int)acc;
+}
+
 }  // namespace yolo
 
 using namespace yolo;
@@ -911,33 +1119,20 @@ extern "C" size_t yolo_nms_workspace_bytes(int n, int class_num) {
   return nms_carve(n, class_num, nullptr, nullptr);
 }
 
-extern "C" int yolo_nms(const double* rows, int n, int class_num, int mode, double nms_threshold,
-                        double conf_threshold, double sigma, unsigned char* keep_out, void* workspace,
-                        size_t workspace_bytes, void* stream) {
-  YOLO_REQUIRE(n >= 0 && class_num > 0, "nms: bad sizes");
-  if (n == 0) return YOLO_OK;
-  YOLO_REQUIRE(rows && keep_out && workspace, "nms: null pointer");
-  YOLO_REQUIRE(mode == YOLO_NMS_HARD || mode == YOLO_NMS_SOFT || mode == YOLO_NMS_DIOU, "nms: bad mode %d", mode);
-  NmsWs ws;
-  const size_t need = nms_carve(n, class_num, workspace, &ws);
-  if (workspace_bytes < need) {
-    set_error("nms: workspace %zu < %zu", workspace_bytes, need);
-    return YOLO_ERR_WORKSPACE;
-  }
-  hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(ws.class_cnt, 0, sizeof(int) * (class_num + 1), st) != hipSuccess) {
+static int nms_zero_counters(const NmsWs& ws, int class_num, hipStream_t st) {
+  if (hipMemsetAsync(ws.class_cnt, 0, sizeof(int) * (class_num + 1), st) != hipSuccess ||
+      hipMemsetAsync(ws.fill, 0, sizeof(int) * (class_num + 1), st) != hipSuccess) {
     set_error("nms: memset failed");
     return YOLO_ERR_LAUNCH;
   }
-  if (hipMemsetAsync(ws.fill, 0, sizeof(int) * (class_num + 1), st) != hipSuccess) {
-    set_error("nms: memset failed");
-    return YOLO_ERR_LAUNCH;
-  }
+  return YOLO_OK;
+}
+
+// Everything behind the prepare kernel and the scan of the counts: bucket, order, pair tests, walk, keep flags. class_num is
+// the number of segments: the classes of one image, or B * class_num for a batch.
+static int nms_resolve(const double* rows, int n, int class_num, int mode, double nms_threshold, double conf_threshold,
+                       double sigma, unsigned char* keep_out, const NmsWs& ws, int force_walk, hipStream_t st) {
   const int nb = (n + 255) / 256;
-  init_options();
-  const int force_walk = g_opt[OPT_NMS_WALK];   // yolo_set_option key 7 (tests): no bit matrices -- the walk / tiled kernels for every class
-  hipLaunchKernelGGL(nms_prepare_kernel, dim3(nb), dim3(256), 0, st, rows, n, class_num, ws);
-  hipLaunchKernelGGL(nms_class_scan_kernel, dim3(1), dim3(64), 0, st, class_num, ws, force_walk ? 0 : 1);
   // workgroups of the pair-matrix kernel: tiles <= sum over classes of T (T + 1) / 2 <= (n / 64 + class_num) (T_max + 1) / 2
   long long mask_grid = 1;
   {
@@ -990,6 +1185,28 @@ extern "C" int yolo_nms(const double* rows, int n, int class_num, int mode, doub
   return check_launch("nms kernels");
 }
 
+extern "C" int yolo_nms(const double* rows, int n, int class_num, int mode, double nms_threshold,
+                        double conf_threshold, double sigma, unsigned char* keep_out, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+  YOLO_REQUIRE(n >= 0 && class_num > 0, "nms: bad sizes");
+  if (n == 0) return YOLO_OK;
+  YOLO_REQUIRE(rows && keep_out && workspace, "nms: null pointer");
+  YOLO_REQUIRE(mode == YOLO_NMS_HARD || mode == YOLO_NMS_SOFT || mode == YOLO_NMS_DIOU, "nms: bad mode %d", mode);
+  NmsWs ws;
+  const size_t need = nms_carve(n, class_num, workspace, &ws);
+  if (workspace_bytes < need) {
+    set_error("nms: workspace %zu < %zu", workspace_bytes, need);
+    return YOLO_ERR_WORKSPACE;
+  }
+  hipStream_t st = as_stream(stream);
+  if (int rc = nms_zero_counters(ws, class_num, st)) return rc;
+  init_options();
+  const int force_walk = g_opt[OPT_NMS_WALK];   // yolo_set_option key 7 (tests): no bit matrices -- the walk / tiled kernels for every class
+  hipLaunchKernelGGL(nms_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rows, n, class_num, ws);
+  hipLaunchKernelGGL(nms_class_scan_kernel, dim3(1), dim3(64), 0, st, class_num, ws, force_walk ? 0 : 1);
+  return nms_resolve(rows, n, class_num, mode, nms_threshold, conf_threshold, sigma, keep_out, ws, force_walk, st);
+}
+
 extern "C" int yolo_nms_select(const double* rows, int n, int class_num, int mode, double nms_threshold,
                                double conf_threshold, double sigma, unsigned char* keep_out, double* rows_out,
                                int* count_out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1014,4 +1231,158 @@ extern "C" int yolo_nms_select(const double* rows, int n, int class_num, int mod
   hipLaunchKernelGGL(nms_kept_scan_kernel, dim3(1), dim3(64), 0, st, class_num, ws, count_out);
   hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, rows, class_num, ws, keep_out, rows_out);
   return check_launch("nms gather kernels");
+}
+
+// ---- batched decode + NMS (utils/tools.py:370-438, 687-786 for every image of a batch) ----
+static bool decode_batch_blocks(int levels, const int* gh, const int* gw, const int* A, int C, int B, int* blk_off) {
+  long long per_image = 0;
+  for (int l = 0; l < levels; ++l) {
+    if (gh[l] <= 0 || gw[l] <= 0 || A[l] <= 0) return false;
+    const long long total = (long long)gh[l] * gw[l] * A[l] * C;
+    if (blk_off) blk_off[l] = (int)per_image;
+    per_image += (total + DEC_BLOCK * DEC_ITEMS - 1) / (DEC_BLOCK * DEC_ITEMS);
+    if (per_image * B > 0x7fffffffLL / 2) return false;
+  }
+  if (blk_off) blk_off[levels] = (int)per_image;
+  return true;
+}
+
+extern "C" size_t yolo_decode_batch_workspace_bytes(int levels, const int* gh, const int* gw, const int* A, int C, int B) {
+  int blk_off[DEC_MAX_LEVELS + 1];
+  if (levels <= 0 || levels > DEC_MAX_LEVELS || !gh || !gw || !A || C <= 0 || B <= 0 ||
+      !decode_batch_blocks(levels, gh, gw, A, C, B, blk_off))
+    return 0;
+  return ((size_t)blk_off[levels] * B + 1) * sizeof(int);
+}
+
+static int decode_batch_args(const void* const* preds, const int* is_f64, int levels, int B, const int* gh, const int* gw,
+                             const int* A, int C, int version, const double* thresholds, const void* workspace,
+                             size_t workspace_bytes, DecodeBatch* d) {
+  YOLO_REQUIRE(preds && is_f64 && gh && gw && A && thresholds && workspace, "decode_batch: null pointer");
+  YOLO_REQUIRE(levels > 0 && levels <= DEC_MAX_LEVELS, "decode_batch: 1 to %d levels, got %d", DEC_MAX_LEVELS, levels);
+  YOLO_REQUIRE(B > 0 && B <= 65535 && C > 0, "decode_batch: bad shape");
+  YOLO_REQUIRE(version >= 1 && version <= 4, "decode_batch: Invalid version: %d", version);
+  YOLO_REQUIRE(decode_batch_blocks(levels, gh, gw, A, C, B, d->blk_off), "decode_batch: bad shape");
+  d->levels = levels;
+  for (int l = 0; l < levels; ++l) {
+    YOLO_REQUIRE(preds[l] != nullptr, "decode_batch: null pointer");
+    const long long D = version == 1 ? 5LL * A[l] + C : (long long)A[l] * (5 + C);
+    d->pred[l] = preds[l];
+    d->g[l] = DecodeGeom{gh[l], gw[l], A[l], C, version, (long long)gh[l] * gw[l] * A[l] * C};
+    d->img_stride[l] = (long long)gh[l] * gw[l] * D;
+    d->thr[l] = thresholds[l];
+    d->f64[l] = is_f64[l] ? 1 : 0;
+  }
+  const size_t need = ((size_t)d->blk_off[levels] * B + 1) * sizeof(int);
+  if (workspace_bytes < need) {
+    set_error("decode_batch: workspace %zu < %zu", workspace_bytes, need);
+    return YOLO_ERR_WORKSPACE;
+  }
+  return YOLO_OK;
+}
+
+extern "C" int yolo_decode_batch_count(const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
+                                       const int* gw, const int* A, int C, int version, const double* thresholds,
+                                       int* img_off, void* workspace, size_t workspace_bytes, void* stream) {
+  YOLO_REQUIRE(img_off != nullptr, "decode_batch: null pointer");
+  DecodeBatch d;
+  if (int rc = decode_batch_args(preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace, workspace_bytes, &d))
+    return rc;
+  int* bc = reinterpret_cast<int*>(workspace);
+  const int per_image = d.blk_off[levels];
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(img_off + B, 0, sizeof(int), st) != hipSuccess) {   // (the scan's carry in: the row count so far)
+    set_error("decode_batch: memset failed");
+    return YOLO_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(decode_batch_count_kernel, dim3((unsigned)per_image, (unsigned)B), dim3(DEC_BLOCK), 0, st, d, bc);
+  hipLaunchKernelGGL(decode_scan_kernel, dim3(1), dim3(1024), 0, st, bc, per_image * B, img_off + B);
+  hipLaunchKernelGGL(decode_batch_offsets_kernel, dim3((B + 1 + 255) / 256), dim3(256), 0, st, bc, per_image, B, img_off + B,
+                     img_off);
+  return check_launch("decode_batch count kernels");
+}
+
+extern "C" int yolo_decode_batch_write(const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
+                                       const int* gw, const int* A, int C, int version, const double* thresholds,
+                                       double* rows_out, int max_rows, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  YOLO_REQUIRE(max_rows >= 0 && (rows_out || max_rows == 0), "decode_batch: null pointer");
+  DecodeBatch d;
+  if (int rc = decode_batch_args(preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace, workspace_bytes, &d))
+    return rc;
+  if (max_rows == 0) return YOLO_OK;
+  hipLaunchKernelGGL(decode_batch_write_kernel, dim3((unsigned)d.blk_off[levels], (unsigned)B), dim3(DEC_BLOCK), 0,
+                     as_stream(stream), d, reinterpret_cast<const int*>(workspace), rows_out, max_rows);
+  return check_launch("decode_batch write kernel");
+}
+
+static bool nms_batch_sizes_ok(int n, int B, int class_num) {
+  return n >= 0 && B > 0 && class_num > 0 && (long long)B * class_num < (1LL << 30);
+}
+
+extern "C" size_t yolo_nms_batch_workspace_bytes(int n, int B, int class_num) {
+  if (n <= 0 || !nms_batch_sizes_ok(n, B, class_num)) return 256;
+  return nms_carve(n, B * class_num, nullptr, nullptr, false);
+}
+
+extern "C" int yolo_nms_batch_prepare(const double* rows, int n, const int* img_off, int B, int class_num,
+                                      long long* mask_words_out, void* workspace, size_t workspace_bytes, void* stream) {
+  YOLO_REQUIRE(nms_batch_sizes_ok(n, B, class_num), "nms_batch: bad sizes");
+  YOLO_REQUIRE(mask_words_out != nullptr, "nms_batch: null pointer");
+  hipStream_t st = as_stream(stream);
+  if (n == 0) {
+    if (hipMemsetAsync(mask_words_out, 0, sizeof(long long), st) != hipSuccess) return YOLO_ERR_LAUNCH;
+    return YOLO_OK;
+  }
+  YOLO_REQUIRE(rows && img_off && workspace, "nms_batch: null pointer");
+  const int segs = B * class_num;
+  NmsWs ws;
+  const size_t need = nms_carve(n, segs, workspace, &ws, false);
+  if (workspace_bytes < need) {
+    set_error("nms_batch: workspace %zu < %zu", workspace_bytes, need);
+    return YOLO_ERR_WORKSPACE;
+  }
+  if (int rc = nms_zero_counters(ws, segs, st)) return rc;
+  init_options();
+  const int force_walk = g_opt[OPT_NMS_WALK];
+  hipLaunchKernelGGL(nms_prepare_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rows, n, img_off, B, class_num, ws);
+  hipLaunchKernelGGL(nms_seg_scan_kernel, dim3(1), dim3(1024), 0, st, segs, ws, force_walk ? 0 : 1, mask_words_out);
+  return check_launch("nms_batch prepare kernels");
+}
+
+extern "C" int yolo_nms_batch_select(const double* rows, int n, int B, int class_num, int mode, double nms_threshold,
+                                     double conf_threshold, double sigma, void* mask, long long mask_words,
+                                     unsigned char* keep_out, double* rows_out, int* kept_off_out, void* workspace,
+                                     size_t workspace_bytes, void* stream) {
+  YOLO_REQUIRE(nms_batch_sizes_ok(n, B, class_num), "nms_batch: bad sizes");
+  YOLO_REQUIRE(kept_off_out != nullptr, "nms_batch: null pointer");
+  YOLO_REQUIRE(mask_words >= 0 && (mask || mask_words == 0), "nms_batch: bad matrix buffer");
+  hipStream_t st = as_stream(stream);
+  if (n == 0) {
+    if (hipMemsetAsync(kept_off_out, 0, sizeof(int) * ((size_t)B + 1), st) != hipSuccess) return YOLO_ERR_LAUNCH;
+    return YOLO_OK;
+  }
+  YOLO_REQUIRE(rows && keep_out && rows_out && workspace, "nms_batch: null pointer");
+  YOLO_REQUIRE(mode == YOLO_NMS_HARD || mode == YOLO_NMS_SOFT || mode == YOLO_NMS_DIOU, "nms_batch: bad mode %d", mode);
+  const int segs = B * class_num;
+  NmsWs ws;
+  const size_t need = nms_carve(n, segs, workspace, &ws, false);
+  if (workspace_bytes < need) {
+    set_error("nms_batch: workspace %zu < %zu", workspace_bytes, need);
+    return YOLO_ERR_WORKSPACE;
+  }
+  ws.mask = reinterpret_cast<unsigned long long*>(mask);
+  init_options();
+  const int force_walk = g_opt[OPT_NMS_WALK];
+  hipLaunchKernelGGL(nms_mask_fit_kernel, dim3(1), dim3(1024), 0, st, segs, ws, mask_words);
+  if (int rc = nms_resolve(rows, n, segs, mode, nms_threshold, conf_threshold, sigma, keep_out, ws, force_walk, st)) return rc;
+  if (hipMemsetAsync(ws.fill, 0, sizeof(int) * (segs + 1), st) != hipSuccess) {
+    set_error("nms_batch: memset failed");
+    return YOLO_ERR_LAUNCH;
+  }
+  const int nb = (n + 255) / 256;
+  hipLaunchKernelGGL(nms_kept_count_kernel, dim3(nb), dim3(256), 0, st, n, segs, ws, keep_out);
+  hipLaunchKernelGGL(nms_kept_scan_batch_kernel, dim3(1), dim3(1024), 0, st, segs, class_num, ws, kept_off_out);
+  hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, rows, segs, ws, keep_out, rows_out);
+  return check_launch("nms_batch gather kernels");
 }

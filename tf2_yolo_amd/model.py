@@ -291,6 +291,33 @@ class Model:
         res = [np.concatenate(a, axis=0) for a in outs]
         return res[0] if self.single_output else res
 
+    def detect(self, x, batch_size=32, precision="fp32", conf_threshold=0.5, nms_mode=1, nms_threshold=0.45, nms_sigma=0.5):
+        """Images in, boxes out: predict's forward, then decode + NMS (nms_mode 0: none, 1: NMS, 2: soft-NMS, 3: DIoU-NMS)
+        of every chunk on the device (tools.detect_batch on the head buffers in place, with the model's own class_num and
+        version). Only the kept rows and their per-image offsets reach the host. Returns a list of len(x) float64 arrays
+        (n_i, 7): x, y, w, h, confidence, class index, class probability -- image i's array is what tools.decode + nms of
+        predict(x)'s slices give."""
+        from . import tools
+        precision_enum(precision)
+        if self.version not in (1, 2, 3, 4):
+            raise ValueError("detect needs a detector: this model is a backbone classifier (version 0)")
+        if nms_mode not in (0, 1, 2, 3):
+            raise ValueError(f"Invalid nms_mode: {nms_mode} (0: none, 1: NMS, 2: soft-NMS, 3: DIoU-NMS)")
+        class_num = next(u.C for u in self.net.units if u.kind == "head")
+        if hasattr(x, "__getitem__") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor)):
+            chunks = [x[i][0] for i in range(len(x))]     # Sequence of (img, label) batches, as predict
+        else:
+            chunks = [x[i:i + batch_size] for i in range(0, len(x), batch_size)]
+        res = []
+        for c in chunks:
+            outs = self.net.infer(_to_input(c), precision=precision)
+            rows, offs = tools._detect_batch_flat(outs, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma,
+                                                  self.version)
+            # (the copy below ends this chunk's work on the stream before the next infer overwrites the head buffers)
+            rows = rows.cpu().numpy()
+            res += [rows[int(offs[b]):int(offs[b + 1])] for b in range(len(offs) - 1)]
+        return res
+
     # ---- training ----
     def compile(self, optimizer="adam", loss=None, metrics=None, **_):
         if isinstance(optimizer, str):

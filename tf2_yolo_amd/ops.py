@@ -1370,6 +1370,60 @@ def nms_select(rows, class_num, mode, nms_threshold, conf_threshold=0.5, sigma=0
     return out[:int(count.item())]
 
 
+def decode_batch(levels, anchors_per_level, C, version, thresholds):
+    """levels: CUDA tensors [B, gh, gw, D], float32 or float64 each; anchors_per_level, thresholds: one entry per level.
+    Every image's rows in ONE count -> scan -> write sequence: returns (rows float64 [n, 7] image-major, in per-image
+    decode order inside an image; img_off int32 CUDA tensor [B + 1], the first row of every image). One host sync (n)."""
+    L, B, dev = len(levels), int(levels[0].shape[0]), levels[0].device
+    for lv in levels:
+        if not (lv.is_cuda and lv.is_contiguous() and lv.dtype in (torch.float32, torch.float64)):
+            raise YoloHipError(f"decode_batch: expected contiguous float32 / float64 CUDA tensors, got {lv.dtype} {lv.device}")
+    lib = _lib.load()
+    ints = lambda v: (ctypes.c_int * L)(*[int(a) for a in v])
+    preds = (c_void_p * L)(*[lv.data_ptr() for lv in levels])
+    f64 = ints(lv.dtype == torch.float64 for lv in levels)
+    gh, gw, A = ints(lv.shape[1] for lv in levels), ints(lv.shape[2] for lv in levels), ints(anchors_per_level)
+    thr = (ctypes.c_double * L)(*[float(t) for t in thresholds])
+    nbytes = int(lib.yolo_decode_batch_workspace_bytes(L, gh, gw, A, C, B))
+    if nbytes == 0:
+        raise YoloHipError("decode_batch: bad shape")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    img_off = torch.empty(B + 1, device=dev, dtype=torch.int32)
+    check(lib.yolo_decode_batch_count(preds, f64, L, B, gh, gw, A, C, version, thr, _p(img_off), _p(ws), nbytes, _stream()),
+          "yolo_decode_batch_count")
+    n = int(img_off[B].item())
+    rows = torch.empty((n, 7), device=dev, dtype=torch.float64)
+    check(lib.yolo_decode_batch_write(preds, f64, L, B, gh, gw, A, C, version, thr, _p(rows), n, _p(ws), nbytes, _stream()),
+          "yolo_decode_batch_write")
+    return rows, img_off
+
+
+def nms_batch_select(rows, img_off, class_num, mode, nms_threshold, conf_threshold=0.5, sigma=0.5):
+    """rows: float64 CUDA tensor [n, 7] of B images, image-major; img_off: int32 CUDA tensor [B + 1] (decode_batch). NMS
+    per (image, class) and the ordered gather for the whole batch: returns (kept rows float64 [k, 7] -- the per-image
+    nms_select outputs concatenated --, kept_off int32 NumPy array [B + 1]). Two host syncs, whatever B: the words of the
+    bit matrices (sized from the segment counts) and the offsets of the kept rows."""
+    n, B, dev = int(rows.shape[0]), int(img_off.shape[0]) - 1, rows.device
+    if n == 0:
+        return rows.reshape(0, 7), torch.zeros(B + 1, dtype=torch.int32).numpy()
+    lib = _lib.load()
+    nbytes = int(lib.yolo_nms_batch_workspace_bytes(n, B, class_num))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    words = torch.empty(1, device=dev, dtype=torch.int64)
+    check(lib.yolo_nms_batch_prepare(_p(rows), n, _p(img_off), B, class_num, _p(words), _p(ws), nbytes, _stream()),
+          "yolo_nms_batch_prepare")
+    mask_words = int(words.item())
+    mask = torch.empty(max(mask_words, 1), device=dev, dtype=torch.int64)
+    keep = torch.empty(n, device=dev, dtype=torch.uint8)
+    out = torch.empty((n, 7), device=dev, dtype=torch.float64)
+    kept_off = torch.empty(B + 1, device=dev, dtype=torch.int32)
+    check(lib.yolo_nms_batch_select(_p(rows), n, B, class_num, mode, float(nms_threshold), float(conf_threshold), float(sigma),
+                                    _p(mask), mask_words, _p(keep), _p(out), _p(kept_off), _p(ws), nbytes, _stream()),
+          "yolo_nms_batch_select")
+    offs = kept_off.cpu().numpy()
+    return out[:int(offs[B])], offs
+
+
 # ---- evaluation after decode / NMS (csrc/measure.hip) ---------------------------------------------------
 def match_detections(gt_rows, det_rows, class_num, iou_threshold, class_counts):
     """gt_rows [ngt,7], det_rows [ndet,7] float64 CUDA tensors of ONE image; class_counts int64 CUDA tensor

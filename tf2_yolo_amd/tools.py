@@ -3,6 +3,8 @@
   decode    utils/tools.py:370-438      nms       utils/tools.py:687-733
   soft_nms  utils/tools.py:736-786      (nms with iou_mode=2 is DIoU-NMS)
   cal_iou   utils/tools.py:630-684      (broadcasting IoU / DIoU matrix)
+  detect_batch  decode + NMS of every image of a batch in one pass on the device (not in the reference: its decode and
+                nms take one image); image b's result is decode + nms of the slices label_data[b], bit for bit
 
 Same names, argument meaning, return types (NumPy float64 arrays of shape (n, 7)) and error
 behaviour (ValueError("Invalid version: ...")). Inputs may be NumPy arrays (uploaded) or CUDA
@@ -128,6 +130,64 @@ def _detections(label_datas, class_num, conf_threshold, nms_mode, nms_threshold,
         elif nms_mode == 3:
             rows = nms(rows, class_num, nms_threshold, 2)
     return rows.cpu().numpy().reshape(-1, 7)
+
+
+# ---- a whole batch: decode + NMS without leaving the device ------------------------------------------------
+_NMS_MODES = {1: NMS_HARD, 2: NMS_SOFT, 3: NMS_DIOU}
+
+
+def _check_batch_args(label_datas, nms_mode, version):
+    """the argument errors of detect_batch, raised before anything touches the device"""
+    if version not in (1, 2, 3, 4):
+        raise ValueError(f"Invalid version: {version}")
+    if nms_mode not in (0, 1, 2, 3):
+        raise ValueError(f"Invalid nms_mode: {nms_mode} (0: none, 1: NMS, 2: soft-NMS, 3: DIoU-NMS)")
+    if not label_datas:
+        raise ValueError("detect_batch needs at least one level")
+    shapes = [tuple(a.shape) if torch.is_tensor(a) else np.shape(a) for a in label_datas]
+    for s in shapes:
+        if len(s) != 4:
+            raise ValueError(f"each label_data must have shape (batch, grid_heights, grid_widths, info), got {s}")
+    if len({s[0] for s in shapes}) != 1:
+        raise ValueError(f"the levels hold different batch sizes: {[s[0] for s in shapes]}")
+    return shapes[0][0]
+
+
+def _detect_batch_flat(label_datas, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma, version):
+    """-> (rows float64 CUDA tensor [k, 7] of the whole batch, image-major; NumPy int offsets [B + 1] of the images in it).
+    Three host syncs, whatever the batch size: the candidate count, the words of the bit matrices, the kept offsets."""
+    B = _check_batch_args(label_datas, nms_mode, version)
+    dev = _device()
+    if B == 0:
+        return torch.empty((0, 7), device=dev, dtype=torch.float64), np.zeros(1, dtype=np.int32)
+    levels = [_to_dev(a) for a in label_datas]
+    anchors = [(lv.shape[3] - class_num) // 5 if version == 1 else lv.shape[3] // (5 + class_num) for lv in levels]
+    # the threshold meets the product conf * prob in the level's own type (decode_device)
+    thrs = [float(np.float32(conf_threshold)) if lv.dtype == torch.float32 else float(conf_threshold) for lv in levels]
+    rows, img_off = ops.decode_batch(levels, anchors, class_num, version, thrs)
+    if nms_mode == 0 or rows.shape[0] == 0:
+        return rows, img_off.cpu().numpy()
+    return ops.nms_batch_select(rows, img_off, class_num, _NMS_MODES[nms_mode], nms_threshold, conf_threshold, nms_sigma)
+
+
+def detect_batch_device(*label_datas, class_num=1, conf_threshold=0.5, nms_mode=0, nms_threshold=0.45, nms_sigma=0.5,
+                        version=3):
+    """GPU-resident detect_batch: a list of B float64 CUDA tensors (n_i, 7), views of one buffer."""
+    rows, offs = _detect_batch_flat(label_datas, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma, version)
+    return [rows[int(offs[b]):int(offs[b + 1])] for b in range(len(offs) - 1)]
+
+
+def detect_batch(*label_datas, class_num=1, conf_threshold=0.5, nms_mode=0, nms_threshold=0.45, nms_sigma=0.5, version=3):
+    """decode (utils/tools.py:370-438) + NMS (nms_mode 0: none, 1: NMS, 2: soft-NMS, 3: DIoU-NMS; utils/tools.py:687-786)
+    of every image of a batch in one pass on the device. label_datas: the levels as (B, gh, gw, info) NumPy arrays (uploaded)
+    or CUDA tensors (used in place). Returns a list of B float64 arrays (n_i, 7), shape (0, 7) for an image without
+    detections -- image b's array is what decode + nms of the slices label_data[b] give, bit for bit. NumPy in -> NumPy
+    out; CUDA tensors in -> CUDA tensors out."""
+    was_numpy = not any(torch.is_tensor(a) for a in label_datas)
+    rows, offs = _detect_batch_flat(label_datas, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma, version)
+    if was_numpy:
+        rows = rows.cpu().numpy()
+    return [rows[int(offs[b]):int(offs[b + 1])] for b in range(len(offs) - 1)]
 
 
 def _pixel_boxes(rows, img_size):

@@ -4,6 +4,7 @@ array_to_xml), and explicit errors for the file readers / plotting that SURVEY.m
 (they need cv2 / imgaug / bs4 / matplotlib image I/O, absent in this environment)."""
 from tf2_yolo_amd.labels import down2xlabel, get_class_weight  # noqa: F401  (utils/tools.py:342-367, :592-627)
 from tf2_yolo_amd.tools import array_to_json, array_to_xml, cal_iou, decode, nms, soft_nms  # noqa: F401
+from tf2_yolo_amd.tools import detect_batch  # noqa: F401  (decode + NMS of a whole batch: not in the reference)
 
 EPSILON = 1e-07
 
