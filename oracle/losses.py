@@ -10,12 +10,23 @@ TensorFlow autodiff conventions that matter are made expl
 tf.maximum / tf.minimum send the gradient of a tie to the FIRST operand (`_tf_max/_tf_min`
 select with >= / <=), clip_by_value passes gradient on the closed interval (torch.clamp does
 too), argmax / one_hot / comparisons are constants.
+
+Clip bounds. The reference calls tf.clip_by_value(p, EPSILON, 1 - EPSILON) on float32 tensors: TensorFlow casts the two
+Python floats to the tensor's type, so a prediction is clipped to [float32(1e-7), float32(1 - 1e-7)] = [1.00000001e-7,
+0.99999988]. CLIP_LO / CLIP_HI are those two float32 numbers, held as Python floats; every clip of a confidence or a
+class probability uses them. All arithmetic stays float64 -- only the two constants are what TensorFlow makes of them.
+(With the double 0.9999999 as the upper bound a prediction of 1.0f would give -log(1e-7) = 16.12 where the reference
+gives -log(1.19e-7) = 15.94.) The other uses of EPSILON -- `union + EPSILON`, `_tf_max(..., EPSILON)`, the CIoU atan --
+are additions and maxima, where the float32 rounding of 1e-7 (1.2e-8 relative) is far below the parity bar.
 """
 import math
 
+import numpy as np
 import torch
 
 EPSILON = 1e-07
+CLIP_LO = float(np.float32(EPSILON))        # 1.0000000116860974e-07
+CLIP_HI = float(np.float32(1 - EPSILON))    # 0.9999998807907104
 
 
 def _tf_max(x, y):
@@ -158,7 +169,7 @@ def wrap_yolo_loss_v3(grid_shape, bbox_num, class_num, anchors=None, binary_weig
         xy_loss = _sum_mean0(has_obj_mask_exp * box_loss_scale * (xy_true - xy_pred) ** 2)
         wh_loss = _sum_mean0(has_obj_mask_exp * box_loss_scale * (wh_true - wh_pred) ** 2)
         if use_focal_loss:
-            c_pred = torch.clamp(c_pred, EPSILON, 1 - EPSILON)
+            c_pred = torch.clamp(c_pred, CLIP_LO, CLIP_HI)
             has_obj_c_loss = -_sum_mean0(has_obj_mask * ((1 - c_pred) ** focal_loss_gamma) * torch.log(c_pred))
             no_obj_c_loss = -_sum_mean0(no_obj_mask * (c_pred ** focal_loss_gamma) * torch.log(1 - c_pred))
         else:
@@ -167,7 +178,7 @@ def wrap_yolo_loss_v3(grid_shape, bbox_num, class_num, anchors=None, binary_weig
         c_loss = has_obj_c_loss + binary_weight * no_obj_c_loss
 
         p_true = y_true_[..., -class_num:]
-        p_pred = torch.clamp(y_pred_[..., -class_num:], EPSILON, 1 - EPSILON)
+        p_pred = torch.clamp(y_pred_[..., -class_num:], CLIP_LO, CLIP_HI)
         p_loss = -_sum_mean0(has_obj_mask_exp * (p_true * torch.log(p_pred) + (1 - p_true) * torch.log(1 - p_pred)))
         regularizer = _sum_mean0(wh_pred ** 2) * 0.01
         loss = (loss_weight[0] * xy_loss + loss_weight[1] * wh_loss + loss_weight[2] * c_loss
@@ -202,7 +213,7 @@ def wrap_yolo_loss_v2(grid_shape, bbox_num, class_num, anchors, binary_weight=1,
         no_obj_c_loss = _sum_mean0(no_obj_mask * (0 - c_pred) ** 2)
         c_loss = has_obj_c_loss + binary_weight * no_obj_c_loss
         p_true = y_true_[..., -class_num:]
-        p_pred = torch.clamp(y_pred_[..., -class_num:], EPSILON, 1 - EPSILON)
+        p_pred = torch.clamp(y_pred_[..., -class_num:], CLIP_LO, CLIP_HI)
         p_loss = -_sum_mean0(has_obj_mask_exp * (p_true * torch.log(p_pred)))
         regularizer = _sum_mean0(wh_pred ** 2) * 0.01
         return (loss_weight[0] * xy_loss + loss_weight[1] * wh_loss + loss_weight[2] * c_loss
@@ -227,7 +238,7 @@ def wrap_yolo_loss_v4(grid_shape, bbox_num, class_num, anchors=None, binary_weig
         has_obj_mask_exp = has_obj_mask.unsqueeze(-1)
         no_obj_mask = (1 - has_obj_mask) * (iou_const < ignore_thresh).to(dt)
         box_loss = _sum_mean0(has_obj_mask * (1 - ciou_scores))
-        c_pred = torch.clamp(y_pred_[..., 4], EPSILON, 1 - EPSILON)
+        c_pred = torch.clamp(y_pred_[..., 4], CLIP_LO, CLIP_HI)
         if label_smooth > 0:
             obj_error = torch.abs(1 - label_smooth - c_pred)
             no_obj_error = torch.abs(label_smooth - c_pred)
@@ -238,7 +249,7 @@ def wrap_yolo_loss_v4(grid_shape, bbox_num, class_num, anchors=None, binary_weig
         no_obj_c_loss = -_sum_mean0(no_obj_mask * (no_obj_error ** focal_loss_gamma) * torch.log(1 - no_obj_error))
         c_loss = has_obj_c_loss + binary_weight * no_obj_c_loss
         p_true = y_true_[..., -class_num:]
-        p_pred = torch.clamp(y_pred_[..., -class_num:], EPSILON, 1 - EPSILON)
+        p_pred = torch.clamp(y_pred_[..., -class_num:], CLIP_LO, CLIP_HI)
         p_loss = -_sum_mean0(has_obj_mask_exp * (p_true * torch.log(p_pred) + (1 - p_true) * torch.log(1 - p_pred)))
         wh_pred = torch.log(y_pred_[..., 2:4] / panchors)
         wh_reg = _sum_mean0(wh_pred ** 2)
@@ -269,7 +280,7 @@ def wrap_yolo_loss_v1(grid_shape, bbox_num, class_num, binary_weight=1, loss_wei
         no_obj_c_loss = _sum_mean0(no_obj_mask * (0 - c_pred) ** 2)
         c_loss = has_obj_c_loss + binary_weight * no_obj_c_loss
         p_true = y_true[..., -class_num:].reshape(-1, *grid_shape, class_num)
-        p_pred = torch.clamp(y_pred[..., -class_num:].reshape(-1, *grid_shape, class_num), EPSILON, 1 - EPSILON)
+        p_pred = torch.clamp(y_pred[..., -class_num:].reshape(-1, *grid_shape, class_num), CLIP_LO, CLIP_HI)
         p_loss = -_sum_mean0(has_obj_mask * p_true * torch.log(p_pred))
         return (loss_weight[0] * xy_loss + loss_weight[1] * wh_loss + loss_weight[2] * c_loss
                 + loss_weight[3] * p_loss)

@@ -65,11 +65,12 @@ def loss_inputs(c):
     return yt, yp
 
 
-def loss_case_ious(case, dtype):
-    """OL.cal_iou of every (cell, anchor) of a case, evaluated in `dtype` on the CPU: [cells, A]"""
+def loss_case_ious(case, dtype, inputs=None):
+    """OL.cal_iou of every (cell, anchor) of a case, evaluated in `dtype` on the CPU: [cells, A]. inputs: (y_true, y_pred)
+    of the case's shape where they are not loss_inputs(case) (tests/saturation_cases.py)"""
     import torch
     from oracle import losses as OL
-    yt, yp = loss_inputs(case)
+    yt, yp = loss_inputs(case) if inputs is None else inputs
     gh, gw = case.g
     t = torch.tensor(yt).to(dtype)
     p = torch.tensor(yp).to(dtype)

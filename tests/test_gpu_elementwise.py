@@ -240,9 +240,16 @@ def test_head_act(version, A, C):
     anc = anchors.float().reshape(-1).cuda() if version != 1 else None
     td = t.detach().float().cuda()
     yd = ops.head_act_fwd(td, A, C, version, anc)
-    assert _rel(yd, y.detach()) < TOL
+    # per channel kind, each against its own largest entry: measured against the whole tensor's maximum -- a width, exp(t)
+    # anchor, which can be tens -- a sigmoid or softmax output could be off by 1e-3 and pass
+    from saturation_cases import head_columns
+    cols = head_columns(version, A, C)
+    assert sorted(np.concatenate(list(cols.values())).tolist()) == list(range(D))
+    for kind, c in cols.items():
+        assert _rel(yd[:, c], y.detach()[:, c]) < TOL, kind
     dt = ops.head_act_bwd(yd, dy.float().cuda(), A, C, version, anc)
-    assert _rel(dt, t.grad) < TOL
+    for kind, c in cols.items():
+        assert _rel(dt[:, c], t.grad[:, c]) < TOL, kind
     if version == 4:
         da = torch.zeros(2 * A, device="cuda")
         ops.head_act_bwd(yd, dy.float().cuda(), A, C, version, anc, danchors=da)
