@@ -821,6 +821,23 @@ int yolo_encode_labels(const double* boxes, const int* cls, const int* first, in
 int yolo_down2xlabel(const double* label_in, int N, int gh, int gw, int ch, double* label_out, float* out32,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Network input from raw pixels (no reference counterpart on the device: the reference resizes with
+ * cv2 on the host). out: float32 NHWC [N, H, W, 3] from N packed uint8 RGB images of any sizes in `src` (src_bytes
+ * bytes). table: device array of N 32-byte entries { long long off; int sh, sw, y0, x0, rh, rw; } -- byte offset of
+ * image i in src, its height and width, and the region [y0, y0 + rh) x [x0, x0 + rw) of the output that receives the
+ * image resized to rh x rw: bilinear taps with half-pixel centres and no antialias (cv2 INTER_LINEAR, torch
+ * interpolate(align_corners=False)), coordinates in integer arithmetic, times `rescale`. Every other output value is
+ * float(pad_grey) * rescale. Equal source and region sizes give exactly float(pixel) * rescale. An entry with
+ * non-positive sizes, sides over the limits below, or an extent that leaves [0, src_bytes) is never dereferenced: its
+ * image comes out all pad. One launch on `stream`; float4 stores when W * 3 % 4 == 0 and out is 16-byte aligned.
+ * YOLO_ERR_INVALID_ARG: a null pointer, N, H, W or src_bytes <= 0, H or W over YOLO_IMAGE_MAX_DST, N H W 3 >= 2^31.
+ * ------------------------------------------------------------------------------------ */
+#define YOLO_IMAGE_MAX_SRC 16384   /* source sides  */
+#define YOLO_IMAGE_MAX_DST 4096    /* output and region sides */
+int yolo_image_prepare(const unsigned char* src, long long src_bytes, const void* table, int N, int H, int W,
+                       float rescale, float pad_grey, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

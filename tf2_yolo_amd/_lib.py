@@ -183,6 +183,7 @@ SIGNATURES = {
     "yolo_nms_batch_prepare": (c_int, [_P, c_int, _P, c_int, c_int, _P, _P, c_size_t, _P]),
     "yolo_nms_batch_select": (c_int, [_P, c_int, c_int, c_int, c_int, c_double, c_double, c_double, _P, _LL, _P, _P, _P, _P,
                                       c_size_t, _P]),
+    "yolo_image_prepare": (c_int, [_P, _LL, _P, c_int, c_int, c_int, c_float, c_float, _P, _P]),
 }
 
 _lib = None

@@ -5,6 +5,10 @@ One worker thread gathers each minibatch straight into pinned staging buffers (a
 row gather IS the staging copy), the caller's thread enqueues the H2D copies on a copy stream, and the compute
 stream waits on an event only, so the PCIe transfer of batch i+1 runs under the training step of batch i.
 Staging slots and device buffers are recycled through events; nothing here synchronises the device.
+
+With `rescale` the images stay uint8 all the way to the device (no float32 copy of the data set on the host, a quarter of
+the PCIe bytes): pinned buffers and device sets are typed per array, and csrc/image.hip converts each batch on the compute
+stream, after the event wait, into a float32 buffer kept per device set (images.rescale_on_device).
 """
 import os
 import queue
@@ -27,6 +31,17 @@ def _as_f32_array(a):
     return np.ascontiguousarray(a)
 
 
+def _as_u8_images(a, hw=None):
+    """the x of a feeder with `rescale`: uint8 [n, H, W, 3], kept as it is (images.check_batch raises for anything else)"""
+    from . import images
+    if torch.is_tensor(a):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(images.check_batch(a, hw))
+
+
+_TORCH_DTYPE = {np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8}
+
+
 class _Slot:
     def __init__(self):
         self.bufs = None      # pinned tensors, one per array of the batch
@@ -45,6 +60,7 @@ class FeederBuffers:
         self.slots = [_Slot() for _ in range(_DEPTH)]
         self.dev_sets = [None] * _DEV_SETS
         self.dev_free = [None] * _DEV_SETS    # event: the step that read this set has finished
+        self.dev_x32 = [None] * _DEV_SETS     # with rescale: the float32 images converted from this set's uint8 ones
 
 
 class HostFeeder:
@@ -55,8 +71,9 @@ class HostFeeder:
     `_Yolov3DataSequence`, yolov3/__init__.py:41-53). Yields `(x, [y0, ...])` views of recycled device buffers:
     valid until the next item is requested."""
 
-    def __init__(self, source, buffers=None):
+    def __init__(self, source, buffers=None, rescale=None):
         self.source = source
+        self.rescale = rescale
         self.bufs = buffers if buffers is not None else FeederBuffers()
         self.device, self.copy_stream = self.bufs.device, self.bufs.copy_stream
         self.free = queue.Queue()
@@ -74,9 +91,10 @@ class HostFeeder:
     def _stage(self, slot, tensors, index):
         n = int(index.size) if index is not None else int(tensors[0].shape[0])
         shapes = [(n,) + tuple(t.shape[1:]) for t in tensors]
-        if slot.bufs is None or any(b.shape[0] < n or tuple(b.shape[1:]) != s[1:] for b, s in zip(slot.bufs, shapes)) \
-                or len(slot.bufs) != len(tensors):
-            slot.bufs = [torch.empty(s, dtype=torch.float32).pin_memory() for s in shapes]
+        dtypes = [_TORCH_DTYPE[t.dtype] for t in tensors]
+        if slot.bufs is None or len(slot.bufs) != len(tensors) or any(
+                b.shape[0] < n or tuple(b.shape[1:]) != s[1:] or b.dtype != d for b, s, d in zip(slot.bufs, shapes, dtypes)):
+            slot.bufs = [torch.empty(s, dtype=d).pin_memory() for s, d in zip(shapes, dtypes)]
             slot.host = [b.numpy() for b in slot.bufs]
         t0 = time.perf_counter()
         if slot.copied is not None:
@@ -94,11 +112,17 @@ class HostFeeder:
         self.stats["stage_s"] += time.perf_counter() - t1
         self.stats["batches"] += 1
 
+    def _host_arrays(self, arrays):
+        """float32 host arrays; with rescale the images (the first array) stay uint8"""
+        if self.rescale is None:
+            return [_as_f32_array(a) for a in arrays]
+        return [_as_u8_images(arrays[0])] + [_as_f32_array(a) for a in arrays[1:]]
+
     def _work(self):
         try:
             if self.source[0] == "arrays":
                 _, arrays, order, bs = self.source
-                tensors = [_as_f32_array(a) for a in arrays]
+                tensors = self._host_arrays(arrays)
                 order_t = np.ascontiguousarray(order).astype(np.int64)
                 for i in range(0, len(order), bs):
                     if self.stop:
@@ -112,7 +136,7 @@ class HostFeeder:
                         break
                     ys = list(yb) if isinstance(yb, (list, tuple)) else [yb]
                     slot = self.free.get()
-                    self._stage(slot, [_as_f32_array(a) for a in [xb] + ys], None)
+                    self._stage(slot, self._host_arrays([xb] + ys), None)
                     self.ready.put(slot)
         except BaseException as e:   # surfaced on the consumer's thread
             self.error = e
@@ -138,9 +162,8 @@ class HostFeeder:
             n = slot.n
             dset = self.dev_sets[j]
             if dset is None or len(dset) != len(slot.bufs) or any(
-                    d.shape[0] < n or d.shape[1:] != b.shape[1:] for d, b in zip(dset, slot.bufs)):
-                dset = self.dev_sets[j] = [torch.empty(b.shape, dtype=torch.float32, device=self.device)
-                                           for b in slot.bufs]
+                    d.shape[0] < n or d.shape[1:] != b.shape[1:] or d.dtype != b.dtype for d, b in zip(dset, slot.bufs)):
+                dset = self.dev_sets[j] = [torch.empty(b.shape, dtype=b.dtype, device=self.device) for b in slot.bufs]
                 # fresh blocks may be recycled from tensors the compute stream is still using
                 self.copy_stream.wait_stream(compute)
                 self.dev_free[j] = None
@@ -155,6 +178,14 @@ class HostFeeder:
             self.free.put(slot)
             compute.wait_event(ev)
             views = [d[:n] for d in dset]
+            if self.rescale is not None:
+                # on the compute stream: ordered behind the copy by the event above, and behind the step that last read this
+                # float32 buffer by the stream itself (dev_free[j] keeps the copy stream off the uint8 set until then)
+                from . import images
+                x32 = self.bufs.dev_x32[j]
+                if x32 is None or x32.shape[0] < n or x32.shape[1:] != views[0].shape[1:]:
+                    x32 = self.bufs.dev_x32[j] = torch.empty(dset[0].shape, dtype=torch.float32, device=self.device)
+                views[0] = images.rescale_on_device(views[0], x32[:n], self.rescale)
             yield views[0], views[1:]
             done = torch.cuda.Event()
             done.record(compute)

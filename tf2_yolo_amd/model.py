@@ -22,6 +22,15 @@ def _to_input(x):
     return torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32))).cuda()
 
 
+def _raw_images(x, what):
+    """the image argument of a call with rescale= / resize=: a uint8 batch or a list of uint8 images (images.prepare
+    raises the TypeError for anything else, chunk by chunk); a Sequence of batches has no meaning here"""
+    if not (isinstance(x, (np.ndarray, list, tuple)) or torch.is_tensor(x)):
+        raise TypeError(f"{what} with rescale= / resize= takes a uint8 array [N, h, w, 3] or a list of uint8 images, got "
+                        f"{type(x).__name__}")
+    return x
+
+
 class LayerView:
     """get_layer(name) result: Keras-style weight access onto slices of the flat buffers."""
 
@@ -273,19 +282,42 @@ class Model:
         outs = [t.clone() for t in self.net.forward(_to_input(x), training=training)]
         return outs[0] if self.single_output else outs
 
-    def predict(self, x, batch_size=32, verbose=0, precision="fp32", **_):
+    def _input_hw(self):
+        return (self.net.input.h, self.net.input.w)
+
+    def _prepared_chunks(self, x, batch_size, rescale, resize, pad_grey, what):
+        """raw uint8 images -> (network input, geometry) per chunk of batch_size images, through images.prepare"""
+        from . import images
+        x = _raw_images(x, what)
+        for i in range(0, len(x), batch_size):
+            yield images.prepare(x[i:i + batch_size], self._input_hw(), rescale=rescale, resize=resize, pad_grey=pad_grey)
+
+    def _to_input(self, x, rescale=None):
+        """_to_input, or with rescale: uint8 images already at the network's size, converted on the device"""
+        if rescale is None:
+            return _to_input(x)
+        from . import images
+        return images.prepare(_raw_images(x, "a batch"), self._input_hw(), rescale=rescale, resize=None)[0]
+
+    def predict(self, x, batch_size=32, verbose=0, precision="fp32", rescale=None, resize=None, pad_grey=128, **_):
         """precision: "fp32" (default) or "fp16" -- half-precision inference: every planes convolution runs ONE fp16 MFMA
         pass on its fp16-rounded operands (outputs off by ~3e-4 of their largest entry; DESIGN.md, half-precision
-        inference). __call__ and evaluate stay fp32."""
+        inference). __call__ and evaluate stay fp32.
+        rescale / resize: with either, x is raw pixels -- a uint8 array [N, h, w, 3] or a list of uint8
+        images of any sizes -- resized (None: already the network's size, "stretch", "letterbox" with pad_grey around),
+        multiplied by rescale (None: 1.0) and converted on the device."""
         precision_enum(precision)   # ValueError on anything else (unknown keywords are otherwise ignored here)
-        if hasattr(x, "__getitem__") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor)):
+        raw = rescale is not None or resize is not None
+        if raw:
+            chunks = (c for c, _g in self._prepared_chunks(x, batch_size, rescale, resize, pad_grey, "predict"))
+        elif hasattr(x, "__getitem__") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor)):
             chunks = [x[i][0] for i in range(len(x))]     # Sequence of (img, label) batches
         else:
             n = len(x)
             chunks = [x[i:i + batch_size] for i in range(0, n, batch_size)]
         outs = None
         for c in chunks:
-            o = self.net.infer(_to_input(c), precision=precision)
+            o = self.net.infer(c if raw else _to_input(c), precision=precision)
             o = [t.cpu().numpy() for t in o]
             outs = [[a] for a in o] if outs is None else [acc + [a] for acc, a in zip(outs, o)]
         res = [np.concatenate(a, axis=0) for a in outs]
@@ -296,26 +328,45 @@ class Model:
         of every chunk on the device (tools.detect_batch on the head buffers in place, with the model's own class_num and
         version). Only the kept rows and their per-image offsets reach the host. Returns a list of len(x) float64 arrays
         (n_i, 7): x, y, w, h, confidence, class index, class probability -- image i's array is what tools.decode + nms of
-        predict(x)'s slices give."""
-        from . import tools
+        predict(x)'s slices give. Raw uint8 images: detect_images."""
+        return self._detect(x, batch_size, precision, conf_threshold, nms_mode, nms_threshold, nms_sigma)
+
+    def detect_images(self, x, rescale=None, resize=None, pad_grey=128, batch_size=32, precision="fp32", conf_threshold=0.5,
+                      nms_mode=1, nms_threshold=0.45, nms_sigma=0.5):
+        """detect on raw pixels: x is a uint8 array [N, h, w, 3], a CUDA uint8 tensor or a list of uint8 images
+        of any sizes; rescale / resize / pad_grey as predict's (resize None: already the network's size). With
+        resize="letterbox" the boxes come back relative to each ORIGINAL image (images.unletterbox), not to the padded
+        network input. The other arguments and the result are detect's."""
+        return self._detect(x, batch_size, precision, conf_threshold, nms_mode, nms_threshold, nms_sigma,
+                            raw=(rescale, resize, pad_grey))
+
+    def _detect(self, x, batch_size, precision, conf_threshold, nms_mode, nms_threshold, nms_sigma, raw=None):
+        from . import images, tools
         precision_enum(precision)
         if self.version not in (1, 2, 3, 4):
             raise ValueError("detect needs a detector: this model is a backbone classifier (version 0)")
         if nms_mode not in (0, 1, 2, 3):
             raise ValueError(f"Invalid nms_mode: {nms_mode} (0: none, 1: NMS, 2: soft-NMS, 3: DIoU-NMS)")
         class_num = next(u.C for u in self.net.units if u.kind == "head")
-        if hasattr(x, "__getitem__") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor)):
+        resize = raw[1] if raw else None
+        if raw:
+            chunks = self._prepared_chunks(x, batch_size, raw[0], resize, raw[2], "detect_images")
+        elif hasattr(x, "__getitem__") and hasattr(x, "__len__") and not isinstance(x, (np.ndarray, torch.Tensor)):
             chunks = [x[i][0] for i in range(len(x))]     # Sequence of (img, label) batches, as predict
         else:
             chunks = [x[i:i + batch_size] for i in range(0, len(x), batch_size)]
         res = []
         for c in chunks:
-            outs = self.net.infer(_to_input(c), precision=precision)
+            c, geom = c if raw else (_to_input(c), None)
+            outs = self.net.infer(c, precision=precision)
             rows, offs = tools._detect_batch_flat(outs, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma,
                                                   self.version)
             # (the copy below ends this chunk's work on the stream before the next infer overwrites the head buffers)
             rows = rows.cpu().numpy()
-            res += [rows[int(offs[b]):int(offs[b + 1])] for b in range(len(offs) - 1)]
+            per_image = [rows[int(offs[b]):int(offs[b + 1])] for b in range(len(offs) - 1)]
+            if resize == "letterbox":
+                per_image = [images.unletterbox(r, g, self._input_hw()) for r, g in zip(per_image, geom)]
+            res += per_image
         return res
 
     # ---- training ----
@@ -451,16 +502,17 @@ class Model:
         self.optimizer.step(grad_scale=scale)
         return self._loss_bufs, mvals
 
-    def train_on_batch(self, x, y, return_dict=False, **_):
-        bufs, mvals = self.train_step_device(_to_input(x), self._labels(y), with_metrics=bool(self.metrics))
+    def train_on_batch(self, x, y, return_dict=False, rescale=None, **_):
+        """rescale: x is uint8 pixels already at the network's size; multiplied by rescale on the device"""
+        bufs, mvals = self.train_step_device(self._to_input(x, rescale), self._labels(y), with_metrics=bool(self.metrics))
         losses = [float(b[0].item()) for b in bufs]
         total = sum(losses)
         flat = [float(v.item()) for ms in (mvals or []) for v in ms]
         res = [total] + (losses if len(losses) > 1 else []) + flat
         return res if len(res) > 1 else res[0]
 
-    def test_on_batch(self, x, y):
-        outs = self.net.forward(_to_input(x), training=False)
+    def test_on_batch(self, x, y, rescale=None):
+        outs = self.net.forward(self._to_input(x, rescale), training=False)
         ys = self._labels(y)
         losses = [float(l(yt, o).item()) for l, o, yt in zip(self.loss, outs, ys)]
         mvals = [float(m(yt, o).item()) for ms, o, yt in zip(self.metrics, outs, ys) for m in ms]
@@ -499,14 +551,20 @@ class Model:
         return ("arrays", [x] + ys, order, batch_size)
 
     def fit(self, x=None, y=None, batch_size=None, epochs=1, verbose=1, validation_data=None, shuffle=True,
-            initial_epoch=0, callbacks=None, **_):
+            initial_epoch=0, callbacks=None, rescale=None, **_):
         """Keras-style training loop (README.md:241-297). Host arrays / Sequences are streamed through
         `feeder.HostFeeder` (pinned staging, copy stream) and the per-batch losses stay on the device until
         the epoch ends, so the loop never waits for the GPU; YOLO_FIT_PIPELINE=0 keeps the plain
-        batch-by-batch loop (`train_on_batch` per batch)."""
+        batch-by-batch loop (`train_on_batch` per batch).
+        rescale: x (and validation_data's x) is uint8 pixels already at the network's size -- fit does not resize, labels are
+        tied to the geometry. The feeder then stages and uploads uint8 (no float32 copy of the data set, a quarter of the
+        PCIe bytes) and csrc/image.hip converts each batch on the compute stream."""
         import os
         from .feeder import FeederBuffers, HostFeeder
         batch_size = batch_size or 32
+        if rescale is not None and y is not None:
+            from . import images
+            images.check_batch(x, self._input_hw())      # before the first batch, not on the worker thread
         rng = np.random.default_rng(0)
         hist = {"loss": []}
         pipelined = os.environ.get("YOLO_FIT_PIPELINE", "1") != "0"
@@ -532,7 +590,7 @@ class Model:
             if src is not None:
                 if getattr(self, "_feed_bufs", None) is None:
                     self._feed_bufs = FeederBuffers()
-                feeder = HostFeeder(src, self._feed_bufs)
+                feeder = HostFeeder(src, self._feed_bufs, rescale=rescale)
                 tot_dev = torch.zeros((), dtype=torch.float64, device="cuda")
                 try:
                     for xb, ys in feeder:
@@ -545,13 +603,13 @@ class Model:
                 tot = float(tot_dev.item())
             else:
                 for xb, yb in self._iter_batches(x, y, batch_size, shuffle, rng):
-                    r = self.train_on_batch(xb, yb)
+                    r = self.train_on_batch(xb, yb, rescale=rescale)
                     tot += r[0] if isinstance(r, list) else r
                     nb += 1
             hist["loss"].append(tot / max(nb, 1))
             msg = f"Epoch {ep + 1}/{epochs} - {time.time() - t0:.1f}s - loss: {hist['loss'][-1]:.4f}"
             if validation_data is not None:
-                v = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, verbose=0)
+                v = self.evaluate(validation_data[0], validation_data[1], batch_size=batch_size, verbose=0, rescale=rescale)
                 hist.setdefault("val_loss", []).append(v[0] if isinstance(v, list) else v)
                 msg += f" - val_loss: {hist['val_loss'][-1]:.4f}"
             if verbose:
@@ -563,11 +621,11 @@ class Model:
         self.history = type("History", (), {"history": hist})()
         return self.history
 
-    def evaluate(self, x=None, y=None, batch_size=None, verbose=1, **_):
+    def evaluate(self, x=None, y=None, batch_size=None, verbose=1, rescale=None, **_):
         batch_size = batch_size or 32
         acc, nb = None, 0
         for xb, yb in self._iter_batches(x, y, batch_size, False, None):
-            r = self.test_on_batch(xb, yb)
+            r = self.test_on_batch(xb, yb, rescale=rescale)
             acc = r if acc is None else [a + b for a, b in zip(acc, r)]
             nb += 1
         res = [a / max(nb, 1) for a in acc]

@@ -886,6 +886,19 @@ def fill(t, value):
     check(_lib.load().yolo_fill(_p(t), t.numel(), float(value), _stream()), "yolo_fill")
 
 
+def image_prepare(src, src_bytes, table, n, out, rescale, pad_grey):
+    """packed uint8 RGB images `src` (device, src_bytes bytes) + their device `table` (32 bytes per image) -> float32 NHWC
+    `out` [n, H, W, 3]: resize into each image's region, pad, rescale (csrc/image.hip, tf2_yolo_amd/images.py)"""
+    if src.dtype != torch.uint8 or table.dtype != torch.uint8 or not (src.is_cuda and table.is_cuda):
+        raise YoloHipError("image_prepare: src and table must be uint8 device tensors")
+    _chk_f32(out)
+    if out.dim() != 4 or out.shape[0] != n or out.shape[3] != 3 or table.numel() < 32 * n or src.numel() < src_bytes:
+        raise YoloHipError("image_prepare: bad sizes")
+    check(_lib.load().yolo_image_prepare(_p(src), src_bytes, _p(table), n, out.shape[1], out.shape[2], float(rescale),
+                                         float(pad_grey), _p(out), _stream()), "yolo_image_prepare")
+    return out
+
+
 def zero_bytes(t):
     """all-zero bit pattern over a contiguous tensor of any 4- or 8-byte dtype (the library's own fill kernel: no torch
     operator runs on the product path)"""
