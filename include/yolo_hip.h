@@ -682,7 +682,8 @@ int yolo_sgd_step_clip(float* p, float* g, float* accum, int nesterov, const lon
 /* One level: pred [gh,gw,A*(5+C)] float32 (version 2/3/4) or [gh,gw,5B+C] (version 1).
  * Appends rows (x,y,w,h,conf,class,prob) as float64 to rows_out[7*row] starting at row *count
  * (device int, caller-zeroed before the first level), in the reference's C order
- * (y, x, box, class). Rows beyond max_rows are counted but not written. */
+ * (y, x, box, class). Rows beyond max_rows are counted but not written.
+ * (The count -> scan -> write sequence of yolo_decode_batch_* below with one level and one image; *count is its carry-in.) */
 int yolo_decode_level(const float* pred, int gh, int gw, int A, int C, int version,
                       float threshold, double* rows_out, int max_rows, int* count,
                       void* workspace, size_t workspace_bytes, void* stream);
@@ -729,9 +730,10 @@ int yolo_decode_batch_count(const void* const* preds, const int* is_f64, int lev
 int yolo_decode_batch_write(const void* const* preds, const int* is_f64, int levels, int B, const int* gh, const int* gw,
                             const int* A, int C, int version, const double* thresholds, double* rows_out, int max_rows,
                             void* workspace, size_t workspace_bytes, void* stream);
-/* NMS + gather of a batch's rows (utils/tools.py:687-786 per image): the kernels of yolo_nms_select over B * class_num
- * segments, segment = image * class_num + class, image of row i from img_off (device int [B + 1], rows image-major as
- * yolo_decode_batch_write stores them). The bit matrices are sized from the segment counts, not from n:
+/* NMS + gather of a batch's rows (utils/tools.py:687-786 per image): one pipeline over B * class_num segments,
+ * segment = image * class_num + class, image of row i from img_off (device int [B + 1], rows image-major as
+ * yolo_decode_batch_write stores them); yolo_nms / yolo_nms_select are that pipeline with B = 1 (no img_off) and the
+ * worst-case matrices inside their workspace. Here the bit matrices are sized from the segment counts, not from n:
  *   yolo_nms_batch_prepare  counts and scans the segments; *mask_words_out (device) <- the 64-bit words the matrices take
  *   yolo_nms_batch_select   (same rows, n, B, class_num, same untouched workspace) `mask` = device buffer of `mask_words`
  *                           words (fewer than asked for, or NULL / 0: every segment takes the walk kernels, same

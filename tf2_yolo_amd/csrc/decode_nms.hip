@@ -115,16 +115,6 @@ __device__ __forceinline__ void decode_thread_write(const T* __restrict__ pred, 
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(DEC_BLOCK) void decode_count_kernel(const T* __restrict__ pred, DecodeGeom g, T thr,
-                                                                 int* __restrict__ block_counts) {
-  __shared__ int wsum[DEC_BLOCK / 64];
-  const long long base = ((long long)blockIdx.x * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
-  bool flag[DEC_ITEMS];
-  const int t = decode_block_sum(decode_thread_flags(pred, g, thr, base, flag), wsum);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = t;
-}
-
 // single block: exclusive scan of block_counts[nb] in place, offset by *count; *count += total
 __global__ void decode_scan_kernel(int* __restrict__ block_counts, int nb, int* __restrict__ count) {
   __shared__ int carry;
@@ -151,41 +141,39 @@ __global__ void decode_scan_kernel(int* __restrict__ block_counts, int nb, int* 
   if (threadIdx.x == 0) *count = carry;
 }
 
-template <typename T>
-__global__ __launch_bounds__(DEC_BLOCK) void decode_write_kernel(const T* __restrict__ pred, DecodeGeom g, T thr,
-                                                                 const int* __restrict__ block_offsets,
-                                                                 double* __restrict__ rows, int max_rows) {
-  __shared__ int wsum[DEC_BLOCK / 64];
-  const long long base = ((long long)blockIdx.x * DEC_BLOCK + threadIdx.x) * DEC_ITEMS;
-  bool flag[DEC_ITEMS];
-  const int cnt = decode_thread_flags(pred, g, thr, base, flag);
-  decode_thread_write(pred, g, base, flag, cnt, block_offsets[blockIdx.x], wsum, rows, max_rows);
-}
-
-// ---- a whole batch: every level's [B, gh, gw, D] tensor in ONE count -> scan -> write sequence ----
+// ---- count and write: every level's [B, gh, gw, D] tensor in ONE count -> scan -> write sequence ----
 // A workgroup never straddles an image or a level: grid.y is the image, grid.x runs over the levels' workgroups one level
 // after the other (DecodeBatch::blk_off). The counts are stored image-major -- block_counts[image * blocks + blockIdx.x] --
 // so that ONE flat exclusive scan (decode_scan_kernel) puts the rows image-major, levels in argument order inside an image
 // and (y, x, box, class) inside a level: the per-image outputs concatenated. The scanned entry of an image's first workgroup
-// is the image's first row (decode_batch_offsets_kernel).
+// is the image's first row (decode_batch_offsets_kernel). One level of one image (yolo_decode_level) is the same sequence
+// with levels = 1 and grid.y = 1; there the scan's carry-in appends the rows behind those of the levels decoded before.
 constexpr int DEC_MAX_LEVELS = 8;
+// L = the levels the block has room for: DEC_MAX_LEVELS for a batch, 1 for yolo_decode_level -- the same kernels with an
+// argument block of 72 bytes instead of 520. Measured (profiles/decode_nms_one_pipeline.json "three_way"):
+// with the 520-byte block a three-level decode_device call took 0.139 / 0.138 / 0.286 ms where the parent's per-image
+// kernels took 0.135 / 0.132 / 0.272 (medians of seven processes; slower in all six medians of two runs, its fastest
+// process at the second figure slower than the parent's median), with this form 0.136 / 0.134 / 0.275.
+template <int L>
 struct DecodeBatch {
-  const void* pred[DEC_MAX_LEVELS];
-  DecodeGeom g[DEC_MAX_LEVELS];
-  long long img_stride[DEC_MAX_LEVELS];   // elements of one image: gh * gw * D
-  double thr[DEC_MAX_LEVELS];             // (for a float32 level: a value float32 holds exactly)
-  int f64[DEC_MAX_LEVELS];
-  int blk_off[DEC_MAX_LEVELS + 1];        // first workgroup of a level inside an image; [levels] = workgroups per image
+  const void* pred[L];
+  DecodeGeom g[L];
+  long long img_stride[L];   // elements of one image: gh * gw * D
+  double thr[L];             // (for a float32 level: a value float32 holds exactly)
+  int f64[L];
+  int blk_off[L + 1];        // first workgroup of a level inside an image; [levels] = workgroups per image
   int levels;
 };
 
-__device__ __forceinline__ int decode_batch_level(const DecodeBatch& d) {
+template <int L>
+__device__ __forceinline__ int decode_batch_level(const DecodeBatch<L>& d) {
   int l = 0;
   while (l + 1 < d.levels && (int)blockIdx.x >= d.blk_off[l + 1]) ++l;
   return l;
 }
 
-__global__ __launch_bounds__(DEC_BLOCK) void decode_batch_count_kernel(DecodeBatch d, int* __restrict__ block_counts) {
+template <int L>
+__global__ __launch_bounds__(DEC_BLOCK) void decode_batch_count_kernel(DecodeBatch<L> d, int* __restrict__ block_counts) {
   __shared__ int wsum[DEC_BLOCK / 64];
   const int l = decode_batch_level(d);
   const DecodeGeom g = d.g[l];
@@ -206,7 +194,8 @@ __global__ void decode_batch_offsets_kernel(const int* __restrict__ block_offset
   else if (b == B) img_off[B] = *count;
 }
 
-__global__ __launch_bounds__(DEC_BLOCK) void decode_batch_write_kernel(DecodeBatch d, const int* __restrict__ block_offsets,
+template <int L>
+__global__ __launch_bounds__(DEC_BLOCK) void decode_batch_write_kernel(DecodeBatch<L> d, const int* __restrict__ block_offsets,
                                                                        double* __restrict__ rows, int max_rows) {
   __shared__ int wsum[DEC_BLOCK / 64];
   const int l = decode_batch_level(d);
@@ -294,17 +283,37 @@ static size_t nms_carve(int n, int class_num, void* base, NmsWs* ws, bool with_m
 // addresses one by one took 108 us per pass (device-scope atomics on one address queue up)
 constexpr int NMS_LDS_CLASSES = 2048;
 
-__global__ __launch_bounds__(256) void nms_prepare_kernel(const double* __restrict__ rows, int n, int class_num, NmsWs ws) {
+// ---- segments (utils/tools.py:687-786 per image) ----
+// NMS is per class, so NMS of B images is NMS of one image with the segment key image * class_num + class in place of the
+// class: B * class_num segments, and one image is B = 1. Only this kernel looks at a row's class column; everything behind
+// it works from ws.cls / class_cnt / class_off, where "class" means segment. The gather emits "segments ascending, original
+// order inside a segment": image-major, classes ascending inside an image -- the per-image outputs concatenated -- and the
+// tie rule holds because the rows are stored image-major in per-image decode order.
+// img_off[B + 1] is the first row of every image; with B == 1 the search below has nothing to decide and img_off is never
+// read (yolo_nms has none to pass).
+__global__ __launch_bounds__(256) void nms_prepare_batch_kernel(const double* __restrict__ rows, int n,
+                                                                const int* __restrict__ img_off, int B, int class_num,
+                                                                NmsWs ws) {
   __shared__ int s_cnt[NMS_LDS_CLASSES];
-  const bool lds = class_num <= NMS_LDS_CLASSES;
+  const int segs = B * class_num;
+  const bool lds = segs <= NMS_LDS_CLASSES;
   if (lds)
-    for (int c = threadIdx.x; c < class_num; c += 256) s_cnt[c] = 0;
+    for (int c = threadIdx.x; c < segs; c += 256) s_cnt[c] = 0;
   __syncthreads();
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
     const double* r = rows + (long long)i * 7;
     int c = (int)r[5];  // astype("int") truncates toward zero
-    if (c < 0 || c >= class_num) c = -1;
+    if (c < 0 || c >= class_num) {
+      c = -1;
+    } else {
+      int lo = 0, hi = B - 1;   // the last image whose first row is at or before i (an image without rows has an empty range)
+      while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (img_off[mid] <= i) lo = mid; else hi = mid - 1;
+      }
+      c += lo * class_num;
+    }
     ws.cls[i] = c;
     ws.score[i] = r[4] * r[6];
     ws.pos_of[i] = -1;
@@ -316,33 +325,77 @@ __global__ __launch_bounds__(256) void nms_prepare_kernel(const double* __restri
   }
   if (lds) {
     __syncthreads();
-    for (int c = threadIdx.x; c < class_num; c += 256)
+    for (int c = threadIdx.x; c < segs; c += 256)
       if (s_cnt[c] != 0) atomicAdd(&ws.class_cnt[c], s_cnt[c]);
   }
 }
 
-__global__ void nms_class_scan_kernel(int class_num, NmsWs ws, int want_mask) {
-  // single thread: class_num is small (<= a few thousand)
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    int acc = 0, tiles = 0;
-    long long words = 0;
-    for (int c = 0; c < class_num; ++c) {
-      const int nc = ws.class_cnt[c];
-      ws.class_off[c] = acc;
-      acc += nc;
-      ws.tile_off[c] = tiles;
-      if (want_mask && nc > 0 && nc <= NMS_MASK_MAX) {
-        const int T = (nc + 63) >> 6;
-        ws.mask_off[c] = words;
-        words += (long long)nc * T;
-        tiles += T * (T + 1) / 2;
-      } else {
-        ws.mask_off[c] = -1;
-      }
+// inclusive prefix sum of v over a workgroup of 1024 threads (16 waves); total = the workgroup's sum. s_w: 16 entries of LDS.
+__device__ __forceinline__ long long nms_block_scan(long long v, long long* s_w, long long& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  long long incl = v;
+  for (int o = 1; o < 64; o <<= 1) {
+    const long long t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  __syncthreads();   // (the scan before this one has read s_w)
+  if (lane == 63) s_w[wave] = incl;
+  __syncthreads();
+  long long off = 0, tot = 0;
+  for (int w = 0; w < 16; ++w) {
+    const long long x = s_w[w];
+    if (w < wave) off += x;
+    tot += x;
+  }
+  total = tot;
+  return incl + off;
+}
+
+// exclusive scans of the segment counts (class_off), of their tiles (tile_off) and of their matrices' words (mask_off; -1:
+// no matrix): one workgroup, 1024 segments per step, carries in registers. mask_words_out (may be null) tells the host how
+// many words the matrices take: the batched path sizes them from the segment counts.
+__global__ __launch_bounds__(1024) void nms_seg_scan_kernel(int segs, NmsWs ws, int want_mask,
+                                                            long long* __restrict__ mask_words_out) {
+  __shared__ long long s_w[16];
+  long long acc = 0, tiles = 0, words = 0;
+  for (int base = 0; base < segs; base += 1024) {
+    const int c = base + threadIdx.x;
+    const int nc = c < segs ? ws.class_cnt[c] : 0;
+    const bool has = want_mask && nc > 0 && nc <= NMS_MASK_MAX;
+    const long long T = (nc + 63) >> 6;
+    const long long t = has ? T * (T + 1) / 2 : 0;
+    const long long w = has ? (long long)nc * T : 0;
+    long long tot_n, tot_t, tot_w;
+    const long long in_n = nms_block_scan(nc, s_w, tot_n);
+    const long long in_t = nms_block_scan(t, s_w, tot_t);
+    const long long in_w = nms_block_scan(w, s_w, tot_w);
+    if (c < segs) {
+      ws.class_off[c] = (int)(acc + in_n - nc);
+      ws.tile_off[c] = (int)(tiles + in_t - t);
+      ws.mask_off[c] = has ? words + in_w - w : -1;
     }
-    ws.class_off[class_num] = acc;
-    ws.tile_off[class_num] = tiles;
-    ws.mask_off[class_num] = words;
+    acc += tot_n;
+    tiles += tot_t;
+    words += tot_w;
+  }
+  if (threadIdx.x == 0) {
+    ws.class_off[segs] = (int)acc;
+    ws.tile_off[segs] = (int)tiles;
+    ws.mask_off[segs] = words;
+    if (mask_words_out) *mask_words_out = words;
+  }
+}
+
+// The matrices' buffer holds `capacity_words`. If the segments need more (a caller that did not ask, or passed none), no
+// segment gets a matrix: the walk / tiled kernels resolve them all, with the same results. Batched path only: one image's
+// workspace holds the worst case.
+__global__ __launch_bounds__(1024) void nms_mask_fit_kernel(int segs, NmsWs ws, long long capacity_words) {
+  const bool over = ws.mask_off[segs] > capacity_words;
+  __syncthreads();   // (every thread has read the total before the first one overwrites it)
+  if (!over) return;
+  for (int c = threadIdx.x; c <= segs; c += 1024) {
+    ws.mask_off[c] = c < segs ? -1 : 0;
+    ws.tile_off[c] = 0;
   }
 }
 
@@ -882,16 +935,25 @@ __global__ __launch_bounds__(256) void nms_kept_count_kernel(int n, int class_nu
       if (s_cnt[c] != 0) atomicAdd(&ws.fill[c], s_cnt[c]);
   }
 }
-__global__ void nms_kept_scan_kernel(int class_num, NmsWs ws, int* __restrict__ count) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    int acc = 0;
-    for (int c = 0; c < class_num; ++c) {
-      const int k = ws.fill[c];
-      ws.class_cnt[c] = acc;             // (class_cnt is free by now: first output position of the class)
-      acc += k;
+// exclusive scan of the kept counts (one workgroup, 1024 segments per step); *total = the number of kept rows. kept_off (may
+// be null; [B] entries are written, the caller points total at entry B): the first output row of every image's first segment
+__global__ __launch_bounds__(1024) void nms_kept_scan_batch_kernel(int segs, int class_num, NmsWs ws,
+                                                                   int* __restrict__ kept_off, int* __restrict__ total) {
+  __shared__ long long s_w[16];
+  long long acc = 0;
+  for (int base = 0; base < segs; base += 1024) {
+    const int c = base + threadIdx.x;
+    const int k = c < segs ? ws.fill[c] : 0;
+    long long tot;
+    const long long incl = nms_block_scan(k, s_w, tot);
+    if (c < segs) {
+      const int first = (int)(acc + incl - k);
+      ws.class_cnt[c] = first;             // (class_cnt is free by now: first output position of the segment)
+      if (kept_off && c % class_num == 0) kept_off[c / class_num] = first;
     }
-    *count = acc;
+    acc += tot;
   }
+  if (threadIdx.x == 0) *total = (int)acc;
 }
 // one thread per bucket slot: a kept row's place inside its class = the kept rows of the class with a smaller index
 // (tiles of 256 slots through LDS, as nms_rank_kernel)
@@ -937,141 +999,51 @@ __global__ __launch_bounds__(256) void nms_gather_kernel(const double* __restric
   for (int k = 0; k < 7; ++k) dst[k] = src[k];
 }
 
-// ---- a whole batch (utils/tools.py:687-786 per image): the same kernels over B * class_num segments ----
-// NMS is per class, so NMS of B images is the pipeline above with the segment key image * class_num + class. Only the
-// prepare kernel looks at a row's class column; everything else works from ws.cls / class_cnt / class_off. The gather emits
-// "segments ascending, original order inside a segment": image-major, classes ascending inside an image -- the per-image
-// outputs concatenated -- and the tie rule holds because the rows are stored image-major in per-image decode order.
-__global__ __launch_bounds__(256) void nms_prepare_batch_kernel(const double* __restrict__ rows, int n,
-                                                                const int* __restrict__ img_off, int B, int class_num,
-                                                                NmsWs ws) {
-  __shared__ int s_cnt[NMS_LDS_CLASSES];
-  const int segs = B * class_num;
-  const bool lds = segs <= NMS_LDS_CLASSES;
-  if (lds)
-    for (int c = threadIdx.x; c < segs; c += 256) s_cnt[c] = 0;
-  __syncthreads();
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) {
-    const double* r = rows + (long long)i * 7;
-    int c = (int)r[5];  // astype("int") truncates toward zero
-    if (c < 0 || c >= class_num) {
-      c = -1;
-    } else {
-      int lo = 0, hi = B - 1;   // the last image whose first row is at or before i (an image without rows has an empty range)
-      while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (img_off[mid] <= i) lo = mid; else hi = mid - 1;
-      }
-      c += lo * class_num;
-    }
-    ws.cls[i] = c;
-    ws.score[i] = r[4] * r[6];
-    ws.pos_of[i] = -1;
-    ws.removed[i] = 0;
-    if (c >= 0) {
-      if (lds) atomicAdd(&s_cnt[c], 1);
-      else atomicAdd(&ws.class_cnt[c], 1);
-    }
-  }
-  if (lds) {
-    __syncthreads();
-    for (int c = threadIdx.x; c < segs; c += 256)
-      if (s_cnt[c] != 0) atomicAdd(&ws.class_cnt[c], s_cnt[c]);
-  }
-}
-
-// inclusive prefix sum of v over a workgroup of 1024 threads (16 waves); total = the workgroup's sum. s_w: 16 entries of LDS.
-__device__ __forceinline__ long long nms_block_scan(long long v, long long* s_w, long long& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  long long incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const long long t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  __syncthreads();   // (the scan before this one has read s_w)
-  if (lane == 63) s_w[wave] = incl;
-  __syncthreads();
-  long long off = 0, tot = 0;
-  for (int w = 0; w < 16; ++w) {
-    const long long x = s_w[w];
-    if (w < wave) off += x;
-    tot += x;
-  }
-  total = tot;
-  return incl + off;
-}
-
-// nms_class_scan_kernel for thousands of segments: one workgroup, 1024 segments per step, carries in registers. Also tells
-// the host how many words the matrices take (*mask_words_out): the batched path sizes them from the segment counts.
-__global__ __launch_bounds__(1024) void nms_seg_scan_kernel(int segs, NmsWs ws, int want_mask,
-                                                            long long* __restrict__ mask_words_out) {
-  __shared__ long long s_w[16];
-  long long acc = 0, tiles = 0, words = 0;
-  for (int base = 0; base < segs; base += 1024) {
-    const int c = base + threadIdx.x;
-    const int nc = c < segs ? ws.class_cnt[c] : 0;
-    const bool has = want_mask && nc > 0 && nc <= NMS_MASK_MAX;
-    const long long T = (nc + 63) >> 6;
-    const long long t = has ? T * (T + 1) / 2 : 0;
-    const long long w = has ? (long long)nc * T : 0;
-    long long tot_n, tot_t, tot_w;
-    const long long in_n = nms_block_scan(nc, s_w, tot_n);
-    const long long in_t = nms_block_scan(t, s_w, tot_t);
-    const long long in_w = nms_block_scan(w, s_w, tot_w);
-    if (c < segs) {
-      ws.class_off[c] = (int)(acc + in_n - nc);
-      ws.tile_off[c] = (int)(tiles + in_t - t);
-      ws.mask_off[c] = has ? words + in_w - w : -1;
-    }
-    acc += tot_n;
-    tiles += tot_t;
-    words += tot_w;
-  }
-  if (threadIdx.x == 0) {
-    ws.class_off[segs] = (int)acc;
-    ws.tile_off[segs] = (int)tiles;
-    ws.mask_off[segs] = words;
-    *mask_words_out = words;
-  }
-}
-
-// The matrices' buffer holds `capacity_words`. If the segments need more (a caller that did not ask, or passed none), no
-// segment gets a matrix: the walk / tiled kernels resolve them all, with the same results.
-__global__ __launch_bounds__(1024) void nms_mask_fit_kernel(int segs, NmsWs ws, long long capacity_words) {
-  const bool over = ws.mask_off[segs] > capacity_words;
-  __syncthreads();   // (every thread has read the total before the first one overwrites it)
-  if (!over) return;
-  for (int c = threadIdx.x; c <= segs; c += 1024) {
-    ws.mask_off[c] = c < segs ? -1 : 0;
-    ws.tile_off[c] = 0;
-  }
-}
-
-// nms_kept_scan_kernel for thousands of segments, plus the per-image table: kept_off[b] = the first output row of image
-// b's first segment, kept_off[B] = the number of kept rows
-__global__ __launch_bounds__(1024) void nms_kept_scan_batch_kernel(int segs, int class_num, NmsWs ws,
-                                                                   int* __restrict__ kept_off) {
-  __shared__ long long s_w[16];
-  long long acc = 0;
-  for (int base = 0; base < segs; base += 1024) {
-    const int c = base + threadIdx.x;
-    const int k = c < segs ? ws.fill[c] : 0;
-    long long tot;
-    const long long incl = nms_block_scan(k, s_w, tot);
-    if (c < segs) {
-      const int first = (int)(acc + incl - k);
-      ws.class_cnt[c] = first;             // (class_cnt is free by now: first output position of the segment)
-      if (c % class_num == 0) kept_off[c / class_num] = first;
-    }
-    acc += tot;
-  }
-  if (threadIdx.x == 0) kept_off[segs / class_num] = (int)acc;
-}
-
 }  // namespace yolo
 
 using namespace yolo;
+
+// ---- decode (utils/tools.py:370-438): one level of one image, or every level of a batch ----
+static bool decode_batch_blocks(int levels, const int* gh, const int* gw, const int* A, int C, int B, int* blk_off) {
+  long long per_image = 0;
+  for (int l = 0; l < levels; ++l) {
+    if (gh[l] <= 0 || gw[l] <= 0 || A[l] <= 0) return false;
+    const long long total = (long long)gh[l] * gw[l] * A[l] * C;
+    if (blk_off) blk_off[l] = (int)per_image;
+    per_image += (total + DEC_BLOCK * DEC_ITEMS - 1) / (DEC_BLOCK * DEC_ITEMS);
+    if (per_image * B > 0x7fffffffLL / 2) return false;
+  }
+  if (blk_off) blk_off[levels] = (int)per_image;
+  return true;
+}
+
+// What both front ends check and build from their (non-null) arrays of `levels` entries: the argument block with every
+// level's geometry and the workgroup table, and the workspace bound of blk_off[levels] * B + 1 ints. `who` ("decode",
+// "decode_batch") starts the messages.
+template <int L>
+static int decode_geometry(const char* who, const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
+                           const int* gw, const int* A, int C, int version, const double* thresholds,
+                           size_t workspace_bytes, DecodeBatch<L>* d) {
+  YOLO_REQUIRE(B > 0 && B <= 65535 && C > 0, "%s: bad shape", who);
+  YOLO_REQUIRE(version >= 1 && version <= 4, "%s: Invalid version: %d", who, version);
+  YOLO_REQUIRE(decode_batch_blocks(levels, gh, gw, A, C, B, d->blk_off), "%s: bad shape", who);
+  d->levels = levels;
+  for (int l = 0; l < levels; ++l) {
+    YOLO_REQUIRE(preds[l] != nullptr, "%s: null pointer", who);
+    const long long D = version == 1 ? 5LL * A[l] + C : (long long)A[l] * (5 + C);
+    d->pred[l] = preds[l];
+    d->g[l] = DecodeGeom{gh[l], gw[l], A[l], C, version, (long long)gh[l] * gw[l] * A[l] * C};
+    d->img_stride[l] = (long long)gh[l] * gw[l] * D;
+    d->thr[l] = thresholds[l];
+    d->f64[l] = is_f64[l] ? 1 : 0;
+  }
+  const size_t need = ((size_t)d->blk_off[levels] * B + 1) * sizeof(int);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
+    return YOLO_ERR_WORKSPACE;
+  }
+  return YOLO_OK;
+}
 
 extern "C" size_t yolo_decode_workspace_bytes(int gh, int gw, int A, int C) {
   const long long total = (long long)gh * gw * A * C;
@@ -1079,24 +1051,24 @@ extern "C" size_t yolo_decode_workspace_bytes(int gh, int gw, int A, int C) {
   return (size_t)(nb + 1) * sizeof(int);
 }
 
+// One level of one image: levels = 1, grid.y = 1. *count is the scan's carry-in: the rows go behind those of earlier calls
+// (no decode_batch_offsets_kernel: there is one image, and it starts where the caller's count stood).
 template <typename T>
 static int decode_impl(const T* pred, int gh, int gw, int A, int C, int version, T threshold, double* rows_out,
                        int max_rows, int* count, void* workspace, size_t workspace_bytes, void* stream) {
   YOLO_REQUIRE(pred && rows_out && count && workspace, "decode: null pointer");
-  YOLO_REQUIRE(gh > 0 && gw > 0 && A > 0 && C > 0 && max_rows >= 0, "decode: bad shape");
-  YOLO_REQUIRE(version >= 1 && version <= 4, "decode: Invalid version: %d", version);
-  DecodeGeom g{gh, gw, A, C, version, (long long)gh * gw * A * C};
-  const long long nb = (g.total + DEC_BLOCK * DEC_ITEMS - 1) / (DEC_BLOCK * DEC_ITEMS);
-  if (workspace_bytes < (size_t)(nb + 1) * sizeof(int)) {
-    set_error("decode: workspace %zu < %zu", workspace_bytes, (size_t)(nb + 1) * sizeof(int));
-    return YOLO_ERR_WORKSPACE;
-  }
+  YOLO_REQUIRE(gh > 0 && gw > 0 && A > 0 && C > 0 && max_rows >= 0, "decode: bad shape");   // (ahead of the version, as ever)
+  const void* const p = pred;
+  const int f64 = sizeof(T) == sizeof(double) ? 1 : 0;
+  const double thr = threshold;   // (a float threshold widens to double and the kernels narrow it back: exact both ways)
+  DecodeBatch<1> d;
+  if (int rc = decode_geometry("decode", &p, &f64, 1, 1, &gh, &gw, &A, C, version, &thr, workspace_bytes, &d)) return rc;
   int* bc = reinterpret_cast<int*>(workspace);
+  const int nb = d.blk_off[1];
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL((decode_count_kernel<T>), dim3((unsigned)nb), dim3(DEC_BLOCK), 0, st, pred, g, threshold, bc);
-  hipLaunchKernelGGL(decode_scan_kernel, dim3(1), dim3(1024), 0, st, bc, (int)nb, count);
-  hipLaunchKernelGGL((decode_write_kernel<T>), dim3((unsigned)nb), dim3(DEC_BLOCK), 0, st, pred, g, threshold, bc,
-                     rows_out, max_rows);
+  hipLaunchKernelGGL(decode_batch_count_kernel<1>, dim3((unsigned)nb), dim3(DEC_BLOCK), 0, st, d, bc);
+  hipLaunchKernelGGL(decode_scan_kernel, dim3(1), dim3(1024), 0, st, bc, nb, count);
+  hipLaunchKernelGGL(decode_batch_write_kernel<1>, dim3((unsigned)nb), dim3(DEC_BLOCK), 0, st, d, bc, rows_out, max_rows);
   return check_launch("decode kernels");
 }
 
@@ -1114,18 +1086,104 @@ extern "C" int yolo_decode_level_f64(const double* pred, int gh, int gw, int A, 
                              workspace_bytes, stream);
 }
 
+extern "C" size_t yolo_decode_batch_workspace_bytes(int levels, const int* gh, const int* gw, const int* A, int C, int B) {
+  int blk_off[DEC_MAX_LEVELS + 1];
+  if (levels <= 0 || levels > DEC_MAX_LEVELS || !gh || !gw || !A || C <= 0 || B <= 0 ||
+      !decode_batch_blocks(levels, gh, gw, A, C, B, blk_off))
+    return 0;
+  return ((size_t)blk_off[levels] * B + 1) * sizeof(int);
+}
+
+static int decode_batch_args(const void* const* preds, const int* is_f64, int levels, int B, const int* gh, const int* gw,
+                             const int* A, int C, int version, const double* thresholds, const void* workspace,
+                             size_t workspace_bytes, DecodeBatch<DEC_MAX_LEVELS>* d) {
+  YOLO_REQUIRE(preds && is_f64 && gh && gw && A && thresholds && workspace, "decode_batch: null pointer");
+  YOLO_REQUIRE(levels > 0 && levels <= DEC_MAX_LEVELS, "decode_batch: 1 to %d levels, got %d", DEC_MAX_LEVELS, levels);
+  return decode_geometry("decode_batch", preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace_bytes, d);
+}
+
+extern "C" int yolo_decode_batch_count(const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
+                                       const int* gw, const int* A, int C, int version, const double* thresholds,
+                                       int* img_off, void* workspace, size_t workspace_bytes, void* stream) {
+  YOLO_REQUIRE(img_off != nullptr, "decode_batch: null pointer");
+  DecodeBatch<DEC_MAX_LEVELS> d;
+  if (int rc = decode_batch_args(preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace, workspace_bytes, &d))
+    return rc;
+  int* bc = reinterpret_cast<int*>(workspace);
+  const int per_image = d.blk_off[levels];
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(img_off + B, 0, sizeof(int), st) != hipSuccess) {   // (the scan's carry in: the row count so far)
+    set_error("decode_batch: memset failed");
+    return YOLO_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(decode_batch_count_kernel<DEC_MAX_LEVELS>, dim3((unsigned)per_image, (unsigned)B), dim3(DEC_BLOCK), 0, st, d, bc);
+  hipLaunchKernelGGL(decode_scan_kernel, dim3(1), dim3(1024), 0, st, bc, per_image * B, img_off + B);
+  hipLaunchKernelGGL(decode_batch_offsets_kernel, dim3((B + 1 + 255) / 256), dim3(256), 0, st, bc, per_image, B, img_off + B,
+                     img_off);
+  return check_launch("decode_batch count kernels");
+}
+
+extern "C" int yolo_decode_batch_write(const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
+                                       const int* gw, const int* A, int C, int version, const double* thresholds,
+                                       double* rows_out, int max_rows, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  YOLO_REQUIRE(max_rows >= 0 && (rows_out || max_rows == 0), "decode_batch: null pointer");
+  DecodeBatch<DEC_MAX_LEVELS> d;
+  if (int rc = decode_batch_args(preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace, workspace_bytes, &d))
+    return rc;
+  if (max_rows == 0) return YOLO_OK;
+  hipLaunchKernelGGL(decode_batch_write_kernel<DEC_MAX_LEVELS>, dim3((unsigned)d.blk_off[levels], (unsigned)B), dim3(DEC_BLOCK), 0,
+                     as_stream(stream), d, reinterpret_cast<const int*>(workspace), rows_out, max_rows);
+  return check_launch("decode_batch write kernel");
+}
+
+// ---- NMS (utils/tools.py:687-786): one image (B = 1, the bit matrices inside the workspace at their worst-case size) or a
+// batch (the matrices in a buffer of the caller's, sized from the segment counts between the two calls) ----
+static bool nms_sizes_ok(int n, int B, int class_num) {
+  return n >= 0 && B > 0 && class_num > 0 && (long long)B * class_num < (1LL << 30);
+}
+
+static bool nms_mode_ok(int mode) { return mode == YOLO_NMS_HARD || mode == YOLO_NMS_SOFT || mode == YOLO_NMS_DIOU; }
+
 extern "C" size_t yolo_nms_workspace_bytes(int n, int class_num) {
   if (n <= 0 || class_num <= 0) return 256;
   return nms_carve(n, class_num, nullptr, nullptr);
 }
 
-static int nms_zero_counters(const NmsWs& ws, int class_num, hipStream_t st) {
-  if (hipMemsetAsync(ws.class_cnt, 0, sizeof(int) * (class_num + 1), st) != hipSuccess ||
-      hipMemsetAsync(ws.fill, 0, sizeof(int) * (class_num + 1), st) != hipSuccess) {
-    set_error("nms: memset failed");
-    return YOLO_ERR_LAUNCH;
+extern "C" size_t yolo_nms_batch_workspace_bytes(int n, int B, int class_num) {
+  if (n <= 0 || !nms_sizes_ok(n, B, class_num)) return 256;
+  return nms_carve(n, B * class_num, nullptr, nullptr, false);
+}
+
+// (`who` starts the messages of the shared steps below, `what` names their launches in a launch error)
+static int nms_carve_checked(const char* who, int n, int segs, bool with_mask, void* workspace, size_t workspace_bytes,
+                             NmsWs* ws) {
+  const size_t need = nms_carve(n, segs, workspace, ws, with_mask);
+  if (workspace_bytes < need) {
+    set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
+    return YOLO_ERR_WORKSPACE;
   }
   return YOLO_OK;
+}
+
+// The first half: carve the workspace, zero the counters, every row's segment and score with the segment counts (prepare),
+// the scans of the counts. img_off is read only if B > 1. with_mask: the matrices are part of the workspace; otherwise
+// *mask_words_out (may be null) tells the caller how many words to bring.
+static int nms_prepare_scan(const char* who, const char* what, const double* rows, int n, const int* img_off, int B, int class_num,
+                            bool with_mask, long long* mask_words_out, void* workspace, size_t workspace_bytes,
+                            hipStream_t st, NmsWs* ws) {
+  const int segs = B * class_num;
+  if (int rc = nms_carve_checked(who, n, segs, with_mask, workspace, workspace_bytes, ws)) return rc;
+  if (hipMemsetAsync(ws->class_cnt, 0, sizeof(int) * (segs + 1), st) != hipSuccess ||
+      hipMemsetAsync(ws->fill, 0, sizeof(int) * (segs + 1), st) != hipSuccess) {
+    set_error("%s: memset failed", who);
+    return YOLO_ERR_LAUNCH;
+  }
+  init_options();
+  const int force_walk = g_opt[OPT_NMS_WALK];   // yolo_set_option key 7 (tests): no bit matrices -- the walk / tiled kernels for every segment
+  hipLaunchKernelGGL(nms_prepare_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rows, n, img_off, B, class_num, *ws);
+  hipLaunchKernelGGL(nms_seg_scan_kernel, dim3(1), dim3(1024), 0, st, segs, *ws, force_walk ? 0 : 1, mask_words_out);
+  return check_launch(what);
 }
 
 // Everything behind the prepare kernel and the scan of the counts: bucket, order, pair tests, walk, keep flags. class_num is
@@ -1185,26 +1243,40 @@ static int nms_resolve(const double* rows, int n, int class_num, int mode, doubl
   return check_launch("nms kernels");
 }
 
+// The second half, behind nms_resolve: the kept rows in output order. kept_off (may be null) gets the first kept row of
+// each of the B images, *total the number of kept rows.
+static int nms_emit_kept(const char* who, const char* what, const double* rows, int n, int B, int class_num, const NmsWs& ws,
+                         const unsigned char* keep, double* rows_out, int* kept_off, int* total, hipStream_t st) {
+  const int segs = B * class_num, nb = (n + 255) / 256;
+  if (hipMemsetAsync(ws.fill, 0, sizeof(int) * (segs + 1), st) != hipSuccess) {
+    set_error("%s: memset failed", who);
+    return YOLO_ERR_LAUNCH;
+  }
+  hipLaunchKernelGGL(nms_kept_count_kernel, dim3(nb), dim3(256), 0, st, n, segs, ws, keep);
+  hipLaunchKernelGGL(nms_kept_scan_batch_kernel, dim3(1), dim3(1024), 0, st, segs, class_num, ws, kept_off, total);
+  hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, rows, segs, ws, keep, rows_out);
+  return check_launch(what);
+}
+
+// yolo_nms, and the first part of yolo_nms_select: *ws is the carved workspace
+static int nms_image(const double* rows, int n, int class_num, int mode, double nms_threshold, double conf_threshold,
+                     double sigma, unsigned char* keep_out, void* workspace, size_t workspace_bytes, hipStream_t st, NmsWs* ws) {
+  YOLO_REQUIRE(rows && keep_out && workspace, "nms: null pointer");
+  YOLO_REQUIRE(nms_mode_ok(mode), "nms: bad mode %d", mode);
+  if (int rc = nms_prepare_scan("nms", "nms prepare kernels", rows, n, nullptr, 1, class_num, true, nullptr, workspace, workspace_bytes,
+                                st, ws))
+    return rc;
+  return nms_resolve(rows, n, class_num, mode, nms_threshold, conf_threshold, sigma, keep_out, *ws, g_opt[OPT_NMS_WALK], st);
+}
+
 extern "C" int yolo_nms(const double* rows, int n, int class_num, int mode, double nms_threshold,
                         double conf_threshold, double sigma, unsigned char* keep_out, void* workspace,
                         size_t workspace_bytes, void* stream) {
-  YOLO_REQUIRE(n >= 0 && class_num > 0, "nms: bad sizes");
+  YOLO_REQUIRE(nms_sizes_ok(n, 1, class_num), "nms: bad sizes");
   if (n == 0) return YOLO_OK;
-  YOLO_REQUIRE(rows && keep_out && workspace, "nms: null pointer");
-  YOLO_REQUIRE(mode == YOLO_NMS_HARD || mode == YOLO_NMS_SOFT || mode == YOLO_NMS_DIOU, "nms: bad mode %d", mode);
   NmsWs ws;
-  const size_t need = nms_carve(n, class_num, workspace, &ws);
-  if (workspace_bytes < need) {
-    set_error("nms: workspace %zu < %zu", workspace_bytes, need);
-    return YOLO_ERR_WORKSPACE;
-  }
-  hipStream_t st = as_stream(stream);
-  if (int rc = nms_zero_counters(ws, class_num, st)) return rc;
-  init_options();
-  const int force_walk = g_opt[OPT_NMS_WALK];   // yolo_set_option key 7 (tests): no bit matrices -- the walk / tiled kernels for every class
-  hipLaunchKernelGGL(nms_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rows, n, class_num, ws);
-  hipLaunchKernelGGL(nms_class_scan_kernel, dim3(1), dim3(64), 0, st, class_num, ws, force_walk ? 0 : 1);
-  return nms_resolve(rows, n, class_num, mode, nms_threshold, conf_threshold, sigma, keep_out, ws, force_walk, st);
+  return nms_image(rows, n, class_num, mode, nms_threshold, conf_threshold, sigma, keep_out, workspace, workspace_bytes,
+                   as_stream(stream), &ws);
 }
 
 extern "C" int yolo_nms_select(const double* rows, int n, int class_num, int mode, double nms_threshold,
@@ -1217,117 +1289,17 @@ extern "C" int yolo_nms_select(const double* rows, int n, int class_num, int mod
     return YOLO_OK;
   }
   YOLO_REQUIRE(rows_out != nullptr, "nms_select: null pointer");
-  if (int rc = yolo_nms(rows, n, class_num, mode, nms_threshold, conf_threshold, sigma, keep_out, workspace, workspace_bytes,
-                        stream))
-    return rc;
+  YOLO_REQUIRE(nms_sizes_ok(n, 1, class_num), "nms: bad sizes");
   NmsWs ws;
-  nms_carve(n, class_num, workspace, &ws);
-  if (hipMemsetAsync(ws.fill, 0, sizeof(int) * (class_num + 1), st) != hipSuccess) {
-    set_error("nms_select: memset failed");
-    return YOLO_ERR_LAUNCH;
-  }
-  const int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(nms_kept_count_kernel, dim3(nb), dim3(256), 0, st, n, class_num, ws, keep_out);
-  hipLaunchKernelGGL(nms_kept_scan_kernel, dim3(1), dim3(64), 0, st, class_num, ws, count_out);
-  hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, rows, class_num, ws, keep_out, rows_out);
-  return check_launch("nms gather kernels");
-}
-
-// ---- batched decode + NMS (utils/tools.py:370-438, 687-786 for every image of a batch) ----
-static bool decode_batch_blocks(int levels, const int* gh, const int* gw, const int* A, int C, int B, int* blk_off) {
-  long long per_image = 0;
-  for (int l = 0; l < levels; ++l) {
-    if (gh[l] <= 0 || gw[l] <= 0 || A[l] <= 0) return false;
-    const long long total = (long long)gh[l] * gw[l] * A[l] * C;
-    if (blk_off) blk_off[l] = (int)per_image;
-    per_image += (total + DEC_BLOCK * DEC_ITEMS - 1) / (DEC_BLOCK * DEC_ITEMS);
-    if (per_image * B > 0x7fffffffLL / 2) return false;
-  }
-  if (blk_off) blk_off[levels] = (int)per_image;
-  return true;
-}
-
-extern "C" size_t yolo_decode_batch_workspace_bytes(int levels, const int* gh, const int* gw, const int* A, int C, int B) {
-  int blk_off[DEC_MAX_LEVELS + 1];
-  if (levels <= 0 || levels > DEC_MAX_LEVELS || !gh || !gw || !A || C <= 0 || B <= 0 ||
-      !decode_batch_blocks(levels, gh, gw, A, C, B, blk_off))
-    return 0;
-  return ((size_t)blk_off[levels] * B + 1) * sizeof(int);
-}
-
-static int decode_batch_args(const void* const* preds, const int* is_f64, int levels, int B, const int* gh, const int* gw,
-                             const int* A, int C, int version, const double* thresholds, const void* workspace,
-                             size_t workspace_bytes, DecodeBatch* d) {
-  YOLO_REQUIRE(preds && is_f64 && gh && gw && A && thresholds && workspace, "decode_batch: null pointer");
-  YOLO_REQUIRE(levels > 0 && levels <= DEC_MAX_LEVELS, "decode_batch: 1 to %d levels, got %d", DEC_MAX_LEVELS, levels);
-  YOLO_REQUIRE(B > 0 && B <= 65535 && C > 0, "decode_batch: bad shape");
-  YOLO_REQUIRE(version >= 1 && version <= 4, "decode_batch: Invalid version: %d", version);
-  YOLO_REQUIRE(decode_batch_blocks(levels, gh, gw, A, C, B, d->blk_off), "decode_batch: bad shape");
-  d->levels = levels;
-  for (int l = 0; l < levels; ++l) {
-    YOLO_REQUIRE(preds[l] != nullptr, "decode_batch: null pointer");
-    const long long D = version == 1 ? 5LL * A[l] + C : (long long)A[l] * (5 + C);
-    d->pred[l] = preds[l];
-    d->g[l] = DecodeGeom{gh[l], gw[l], A[l], C, version, (long long)gh[l] * gw[l] * A[l] * C};
-    d->img_stride[l] = (long long)gh[l] * gw[l] * D;
-    d->thr[l] = thresholds[l];
-    d->f64[l] = is_f64[l] ? 1 : 0;
-  }
-  const size_t need = ((size_t)d->blk_off[levels] * B + 1) * sizeof(int);
-  if (workspace_bytes < need) {
-    set_error("decode_batch: workspace %zu < %zu", workspace_bytes, need);
-    return YOLO_ERR_WORKSPACE;
-  }
-  return YOLO_OK;
-}
-
-extern "C" int yolo_decode_batch_count(const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
-                                       const int* gw, const int* A, int C, int version, const double* thresholds,
-                                       int* img_off, void* workspace, size_t workspace_bytes, void* stream) {
-  YOLO_REQUIRE(img_off != nullptr, "decode_batch: null pointer");
-  DecodeBatch d;
-  if (int rc = decode_batch_args(preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace, workspace_bytes, &d))
+  if (int rc = nms_image(rows, n, class_num, mode, nms_threshold, conf_threshold, sigma, keep_out, workspace, workspace_bytes,
+                         st, &ws))
     return rc;
-  int* bc = reinterpret_cast<int*>(workspace);
-  const int per_image = d.blk_off[levels];
-  hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(img_off + B, 0, sizeof(int), st) != hipSuccess) {   // (the scan's carry in: the row count so far)
-    set_error("decode_batch: memset failed");
-    return YOLO_ERR_LAUNCH;
-  }
-  hipLaunchKernelGGL(decode_batch_count_kernel, dim3((unsigned)per_image, (unsigned)B), dim3(DEC_BLOCK), 0, st, d, bc);
-  hipLaunchKernelGGL(decode_scan_kernel, dim3(1), dim3(1024), 0, st, bc, per_image * B, img_off + B);
-  hipLaunchKernelGGL(decode_batch_offsets_kernel, dim3((B + 1 + 255) / 256), dim3(256), 0, st, bc, per_image, B, img_off + B,
-                     img_off);
-  return check_launch("decode_batch count kernels");
-}
-
-extern "C" int yolo_decode_batch_write(const void* const* preds, const int* is_f64, int levels, int B, const int* gh,
-                                       const int* gw, const int* A, int C, int version, const double* thresholds,
-                                       double* rows_out, int max_rows, void* workspace, size_t workspace_bytes,
-                                       void* stream) {
-  YOLO_REQUIRE(max_rows >= 0 && (rows_out || max_rows == 0), "decode_batch: null pointer");
-  DecodeBatch d;
-  if (int rc = decode_batch_args(preds, is_f64, levels, B, gh, gw, A, C, version, thresholds, workspace, workspace_bytes, &d))
-    return rc;
-  if (max_rows == 0) return YOLO_OK;
-  hipLaunchKernelGGL(decode_batch_write_kernel, dim3((unsigned)d.blk_off[levels], (unsigned)B), dim3(DEC_BLOCK), 0,
-                     as_stream(stream), d, reinterpret_cast<const int*>(workspace), rows_out, max_rows);
-  return check_launch("decode_batch write kernel");
-}
-
-static bool nms_batch_sizes_ok(int n, int B, int class_num) {
-  return n >= 0 && B > 0 && class_num > 0 && (long long)B * class_num < (1LL << 30);
-}
-
-extern "C" size_t yolo_nms_batch_workspace_bytes(int n, int B, int class_num) {
-  if (n <= 0 || !nms_batch_sizes_ok(n, B, class_num)) return 256;
-  return nms_carve(n, B * class_num, nullptr, nullptr, false);
+  return nms_emit_kept("nms_select", "nms gather kernels", rows, n, 1, class_num, ws, keep_out, rows_out, nullptr, count_out, st);
 }
 
 extern "C" int yolo_nms_batch_prepare(const double* rows, int n, const int* img_off, int B, int class_num,
                                       long long* mask_words_out, void* workspace, size_t workspace_bytes, void* stream) {
-  YOLO_REQUIRE(nms_batch_sizes_ok(n, B, class_num), "nms_batch: bad sizes");
+  YOLO_REQUIRE(nms_sizes_ok(n, B, class_num), "nms_batch: bad sizes");
   YOLO_REQUIRE(mask_words_out != nullptr, "nms_batch: null pointer");
   hipStream_t st = as_stream(stream);
   if (n == 0) {
@@ -1335,26 +1307,16 @@ extern "C" int yolo_nms_batch_prepare(const double* rows, int n, const int* img_
     return YOLO_OK;
   }
   YOLO_REQUIRE(rows && img_off && workspace, "nms_batch: null pointer");
-  const int segs = B * class_num;
   NmsWs ws;
-  const size_t need = nms_carve(n, segs, workspace, &ws, false);
-  if (workspace_bytes < need) {
-    set_error("nms_batch: workspace %zu < %zu", workspace_bytes, need);
-    return YOLO_ERR_WORKSPACE;
-  }
-  if (int rc = nms_zero_counters(ws, segs, st)) return rc;
-  init_options();
-  const int force_walk = g_opt[OPT_NMS_WALK];
-  hipLaunchKernelGGL(nms_prepare_batch_kernel, dim3((n + 255) / 256), dim3(256), 0, st, rows, n, img_off, B, class_num, ws);
-  hipLaunchKernelGGL(nms_seg_scan_kernel, dim3(1), dim3(1024), 0, st, segs, ws, force_walk ? 0 : 1, mask_words_out);
-  return check_launch("nms_batch prepare kernels");
+  return nms_prepare_scan("nms_batch", "nms_batch prepare kernels", rows, n, img_off, B, class_num, false, mask_words_out, workspace,
+                          workspace_bytes, st, &ws);
 }
 
 extern "C" int yolo_nms_batch_select(const double* rows, int n, int B, int class_num, int mode, double nms_threshold,
                                      double conf_threshold, double sigma, void* mask, long long mask_words,
                                      unsigned char* keep_out, double* rows_out, int* kept_off_out, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-  YOLO_REQUIRE(nms_batch_sizes_ok(n, B, class_num), "nms_batch: bad sizes");
+  YOLO_REQUIRE(nms_sizes_ok(n, B, class_num), "nms_batch: bad sizes");
   YOLO_REQUIRE(kept_off_out != nullptr, "nms_batch: null pointer");
   YOLO_REQUIRE(mask_words >= 0 && (mask || mask_words == 0), "nms_batch: bad matrix buffer");
   hipStream_t st = as_stream(stream);
@@ -1363,26 +1325,15 @@ extern "C" int yolo_nms_batch_select(const double* rows, int n, int B, int class
     return YOLO_OK;
   }
   YOLO_REQUIRE(rows && keep_out && rows_out && workspace, "nms_batch: null pointer");
-  YOLO_REQUIRE(mode == YOLO_NMS_HARD || mode == YOLO_NMS_SOFT || mode == YOLO_NMS_DIOU, "nms_batch: bad mode %d", mode);
+  YOLO_REQUIRE(nms_mode_ok(mode), "nms_batch: bad mode %d", mode);
   const int segs = B * class_num;
-  NmsWs ws;
-  const size_t need = nms_carve(n, segs, workspace, &ws, false);
-  if (workspace_bytes < need) {
-    set_error("nms_batch: workspace %zu < %zu", workspace_bytes, need);
-    return YOLO_ERR_WORKSPACE;
-  }
+  NmsWs ws;   // (as yolo_nms_batch_prepare left it)
+  if (int rc = nms_carve_checked("nms_batch", n, segs, false, workspace, workspace_bytes, &ws)) return rc;
   ws.mask = reinterpret_cast<unsigned long long*>(mask);
   init_options();
-  const int force_walk = g_opt[OPT_NMS_WALK];
   hipLaunchKernelGGL(nms_mask_fit_kernel, dim3(1), dim3(1024), 0, st, segs, ws, mask_words);
-  if (int rc = nms_resolve(rows, n, segs, mode, nms_threshold, conf_threshold, sigma, keep_out, ws, force_walk, st)) return rc;
-  if (hipMemsetAsync(ws.fill, 0, sizeof(int) * (segs + 1), st) != hipSuccess) {
-    set_error("nms_batch: memset failed");
-    return YOLO_ERR_LAUNCH;
-  }
-  const int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(nms_kept_count_kernel, dim3(nb), dim3(256), 0, st, n, segs, ws, keep_out);
-  hipLaunchKernelGGL(nms_kept_scan_batch_kernel, dim3(1), dim3(1024), 0, st, segs, class_num, ws, kept_off_out);
-  hipLaunchKernelGGL(nms_gather_kernel, dim3(nb), dim3(256), 0, st, rows, segs, ws, keep_out, rows_out);
-  return check_launch("nms_batch gather kernels");
+  if (int rc = nms_resolve(rows, n, segs, mode, nms_threshold, conf_threshold, sigma, keep_out, ws, g_opt[OPT_NMS_WALK], st))
+    return rc;
+  return nms_emit_kept("nms_batch", "nms_batch gather kernels", rows, n, B, class_num, ws, keep_out, rows_out, kept_off_out,
+                       kept_off_out + B, st);
 }
