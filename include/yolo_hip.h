@@ -796,6 +796,40 @@ int yolo_pr_curve(const double* joint, const int* gt_id, const unsigned char* ma
                   int precision_mode, void* workspace, size_t workspace_bytes, double* precision,
                   double* recall, void* stream);
 
+/* The three calls above for a whole data set (csrc/measure_batch.hip): no launch and no device read per image or per
+ * class. Every value equals what the per-image / per-class call gives, bit for bit.
+ *
+ * yolo_match_batch: rows of B images, image-major, with device offsets gt_off / det_off (int [B + 1], [B] = the row
+ * count) -- what yolo_decode_batch_write and yolo_nms_batch_select store. Per detection best_gt / matched / best_iou as
+ * yolo_match_detections defines them, against the ground truths of its own image and its own class id (in range or
+ * not), and gid = best_gt + (ground truths of that class in earlier images of this call) + gts_seen[class]: the ground
+ * truth's index inside its class over the data set; 0 where the image has no ground truth of the class, best_gt alone
+ * for a class id outside [0, class_num). class_counts as yolo_match_detections (accumulated; the distinct matched
+ * ground truths are counted per image). gts_seen (device long long [class_num], zero before the first call) advances
+ * by this call's ground truths per class. Workspace: one flag byte per ground truth and 2 * B * class_num ints. */
+size_t yolo_match_batch_workspace_bytes(int ngt, int B, int class_num);
+int yolo_match_batch(const double* gt_rows, int ngt, const int* gt_off, const double* det_rows, int ndet,
+                     const int* det_off, int B, int class_num, double iou_threshold, long long* gts_seen, int* best_gt,
+                     unsigned char* matched, double* best_iou, int* gid, long long* class_counts, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+/* yolo_rank_desc with segment = (image, cls[i]): the rank of every row among the rows of its own image (img_off: device
+ * int [B + 1], rows image-major) and class, in yolo_rank_desc's total order. A row is compared against the rows of its
+ * image only. cls may be NULL (one class per image). */
+int yolo_rank_desc_images(const double* key, const int* cls, int n, const int* img_off, int B, int* rank, void* stream);
+
+/* yolo_pr_curve for every class in one call. Row i: joint confidence, gid (yolo_match_batch), matched, cls[i]; a row
+ * whose cls is outside [0, class_num) is passed over. gts: device long long [class_num], the ground truths per class;
+ * gts_total: a host-side upper bound of their sum (it sizes the workspace; ids past it are never marked).
+ * cls_off (device int [class_num + 1]) <- the exclusive scan of the rows per class; precision / recall hold
+ * n + class_num doubles: class c's n_c + 1 points start at cls_off[c] + c and equal yolo_pr_curve on that class's rows
+ * (in their order) with num_gts = gts[c], the closing point included. The slots of a class with n_c = 0 or
+ * gts[c] <= 0 are not written: yolo_pr_curve refuses those too, and the caller fills them in. */
+size_t yolo_pr_curves_workspace_bytes(int n, int class_num, long long gts_total);
+int yolo_pr_curves(const double* joint, const int* gid, const unsigned char* matched, const int* cls, int n,
+                   const long long* gts, int class_num, long long gts_total, int precision_mode, void* workspace,
+                   size_t workspace_bytes, int* cls_off, double* precision, double* recall, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Gradient exchange (data parallelism; no reference counterpart). `yolo_allreduce_bucket` is the thin RCCL wrapper
  * SURVEY.md section 8b lists (round 5; rounds 1-4 left it out): in-place sum all-reduce of `count` fp32 values of the

@@ -172,6 +172,11 @@ SIGNATURES = {
     "yolo_rank_desc": (c_int, [_P, _P, c_int, _P, _P]),
     "yolo_pr_curve_workspace_bytes": (c_size_t, [c_int, c_int]),
     "yolo_pr_curve": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P, _P, _P]),
+    "yolo_match_batch_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "yolo_match_batch": (c_int, [_P, c_int, _P, _P, c_int, _P, c_int, c_int, c_double, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "yolo_rank_desc_images": (c_int, [_P, _P, c_int, _P, c_int, _P, _P]),
+    "yolo_pr_curves_workspace_bytes": (c_size_t, [c_int, c_int, _LL]),
+    "yolo_pr_curves": (c_int, [_P, _P, _P, _P, c_int, _P, c_int, _LL, c_int, _P, c_size_t, _P, _P, _P, _P]),
     "yolo_nms": (c_int, [_P, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, c_size_t, _P]),
     "yolo_nms_select": (c_int, [_P, c_int, c_int, c_int, c_double, c_double, c_double, _P, _P, _P, _P, c_size_t, _P]),
     "yolo_decode_batch_workspace_bytes": (c_size_t, [c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int), c_int, c_int]),
@@ -193,6 +198,7 @@ _QUERIES = {"yolo_last_error", "yolo_last_conv_kernel", "yolo_abi_version", "yol
             "yolo_stem_bwd_scratch_bytes", "yolo_loss_workspace_bytes", "yolo_decode_workspace_bytes",
             "yolo_nms_workspace_bytes", "yolo_pr_curve_workspace_bytes", "yolo_wgrad_workspace_bytes", "yolo_adam_lr_t",
             "yolo_grad_sqnorm_workspace_bytes", "yolo_decode_batch_workspace_bytes", "yolo_nms_batch_workspace_bytes",
+            "yolo_match_batch_workspace_bytes", "yolo_pr_curves_workspace_bytes",
             "yolo_set_option", "yolo_set_debug_buffer", "yolo_set_conv_workspace", "yolo_set_wgrad_workspace"}
 
 

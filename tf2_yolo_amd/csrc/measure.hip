@@ -16,21 +16,9 @@
 //                          slot of the sorted flags is written exactly once), then for every prefix the number
 //                          of matched detections and of DISTINCT matched ground truths -> precision (3 modes)
 //                          and recall, plus the closing (0, last recall) point      (measurement.py:299-323)
-#include "common.hpp"
+#include "measure_common.hpp"   // iou_xywh, shared with measure_batch.hip
 
 namespace yolo {
-
-// utils/tools.py:630-684 (mode 1) in fp64; a = ground truth, b = prediction
-__device__ __forceinline__ double iou_xywh(const double* a, const double* b) {
-  const double ahx = a[2] / 2., ahy = a[3] / 2., bhx = b[2] / 2., bhy = b[3] / 2.;
-  const double aminx = a[0] - ahx, amaxx = a[0] + ahx, aminy = a[1] - ahy, amaxy = a[1] + ahy;
-  const double bminx = b[0] - bhx, bmaxx = b[0] + bhx, bminy = b[1] - bhy, bmaxy = b[1] + bhy;
-  const double iw = fmax(fmin(bmaxx, amaxx) - fmax(bminx, aminx), 0.);
-  const double ih = fmax(fmin(bmaxy, amaxy) - fmax(bminy, aminy), 0.);
-  const double inter = iw * ih;
-  const double uni = b[2] * b[3] + a[2] * a[3] - inter;
-  return inter / (uni + 1e-07);
-}
 
 // one thread per detection, the ground truths of an image are few
 __global__ void match_kernel(const double* __restrict__ gt, int ngt, const double* __restrict__ det, int ndet,

@@ -1,9 +1,11 @@
 """Drop-in for the reference's utils/measurement.py (create_score_mat :16-150, PRfunc :153-447), on the GPU.
 
 Same names, arguments, defaults and return types (pandas DataFrames; PRfunc.precisions / .recalls lists of
-float64 arrays). Per image the pipeline is decode -> NMS -> IoU matching, all in HIP kernels (decode_nms.hip,
-measure.hip); the precision / recall curve of a class is one more kernel over all its detections. The host
-keeps what the reference keeps in Python lists: which rows belong to which image and class.
+float64 arrays). The pipeline is decode -> NMS -> IoU matching -> per-image cap, for a chunk of images at a time and
+all in HIP kernels (decode_nms.hip, measure_batch.hip); the precision / recall curves of all classes are one more call over
+the detections of the whole data set. `Evaluator` is that pipeline as an accumulator (update per chunk, score_mat /
+prfunc at the end; Model.evaluate_detections feeds it the head buffers in place); create_score_mat and PRfunc cut their
+arrays into chunks of EVAL_CHUNK images and feed one. Nothing is launched or read back per image or per class.
 
 Differences, all in corners the reference leaves undefined or broken:
   * exact ties of the joint confidence: the later detection sorts first (np.argsort is unstable), in the per-image
@@ -25,49 +27,152 @@ from . import ops, tools
 from ._lib import YoloHipError
 
 
-def _per_image_rows(y_true, y_pred, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma, version):
-    """decode (+ NMS) of one image -> float64 CUDA tensors (n,7): ground truth rows, detection rows"""
-    gt = tools.decode_device(y_true, class_num=class_num, version=version)
-    det = tools.decode_device(*y_pred, class_num=class_num, threshold=conf_threshold, version=version)
-    if nms_mode > 0 and det.shape[0] > 0:
-        if nms_mode == 1:
-            det = tools.nms(det, class_num, nms_threshold)
-        elif nms_mode == 2:
-            det = tools.soft_nms(det, class_num, nms_threshold, conf_threshold, nms_sigma)
-        elif nms_mode == 3:
-            det = tools.nms(det, class_num, nms_threshold, 2)
-    return gt, det
+EVAL_CHUNK = 256   # images per Evaluator.update of create_score_mat / PRfunc (at 416 x 416 and C = 80: ~0.9 GB of fp32 levels)
 
 
-def _images(y_trues, y_preds):
-    for i_label in range(len(y_trues)):
-        yield y_trues[i_label], [y_preds[j][i_label] for j in range(len(y_preds))]
+def _shape(a):
+    return tuple(a.shape) if torch.is_tensor(a) else np.shape(a)
+
+
+class Evaluator(object):
+    """Detection evaluation of a data set, chunk by chunk, on the device: update(y_true, *y_preds) per chunk of images,
+    then score_mat() (create_score_mat's table) and prfunc() (a PRfunc). The host reads a fixed number of scalars and
+    offsets per chunk (decode_batch, nms_batch_select), whatever the number of images and classes; the per-class counts
+    and the records of the kept detections (joint confidence, ground-truth id, matched, class) stay on the device.
+
+    Per chunk: ground truth through ops.decode_batch (threshold 0.5), detections through tools._detect_batch_flat
+    (decode + NMS), ops.match_batch, the cap of max_per_img detections per image and class (ops.rank_desc_images; None:
+    no cap), and the records are appended. Image b of a chunk is evaluated as create_score_mat / PRfunc evaluate it, bit
+    for bit; the chunking does not enter the result. class_names=[]: nothing to evaluate, empty tables and curves."""
+
+    def __init__(self, class_names, version=3, conf_threshold=0.05, nms_mode=1, nms_threshold=0.5, nms_sigma=0.5,
+                 iou_threshold=0.5, precision_mode=2, max_per_img=100):
+        if version not in (1, 2, 3, 4):
+            raise ValueError(f"Invalid version: {version}")
+        if nms_mode not in (0, 1, 2, 3):
+            raise ValueError(f"Invalid nms_mode: {nms_mode} (0: none, 1: NMS, 2: soft-NMS, 3: DIoU-NMS)")
+        self.class_names = class_names
+        self.class_num = len(class_names)
+        self.version = version
+        self.conf_threshold, self.nms_mode, self.nms_threshold, self.nms_sigma = conf_threshold, nms_mode, nms_threshold, nms_sigma
+        self.iou_threshold, self.precision_mode, self.max_per_img = iou_threshold, precision_mode, max_per_img
+        self.images = 0
+        self._gts = self._counts = None       # int64 [C] / [C, 4] on the device, made by the first update
+        self._gt_rows = 0                     # decoded ground-truth rows so far: a host-side bound of gts.sum()
+        self._records = []                    # per chunk: (joint, gid, matched, cls), cls = -1 where the row is cut
+
+    def update(self, y_true, *y_preds):
+        """one chunk: y_true [B, gh, gw, info], every prediction level [B, ...]; NumPy arrays are uploaded, CUDA tensors are
+        used in place (they are free again when update returns)"""
+        self._update(y_true, y_preds, True)
+
+    def _update(self, y_true, y_preds, records):
+        B = tools._check_batch_args(y_preds, self.nms_mode, self.version)
+        s = _shape(y_true)
+        if len(s) != 4:
+            raise ValueError(f"y_true must have shape (batch, grid_heights, grid_widths, info), got {s}")
+        if s[0] != B:
+            raise ValueError(f"y_true and the prediction levels hold different batch sizes: {s[0]} and {B}")
+        dev = tools._device()
+        C = self.class_num
+        self.images += B
+        if C == 0 or B == 0:
+            return
+        if self._gts is None:
+            self._gts = torch.zeros(C, device=dev, dtype=torch.int64)
+            self._counts = torch.zeros((C, 4), device=dev, dtype=torch.int64)   # dets, gts, tpp, tp
+        y_true = tools._to_dev(y_true)
+        anchors = (s[3] - C) // 5 if self.version == 1 else s[3] // (5 + C)
+        gt, gt_off = ops.decode_batch([y_true], [anchors], C, self.version, [0.5])
+        det, offs = tools._detect_batch_flat(y_preds, C, self.conf_threshold, self.nms_mode, self.nms_threshold,
+                                             self.nms_sigma, self.version)
+        det_off = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.int32)).to(dev)
+        _, matched, _, gid = ops.match_batch(gt, gt_off, det, det_off, C, self.iou_threshold, self._gts, self._counts)
+        self._gt_rows += int(gt.shape[0])
+        if not records or det.shape[0] == 0:
+            return
+        cls = det[:, 5].to(torch.int32)
+        joint = (det[:, 4] * det[:, 6]).contiguous()
+        keep = (cls >= 0) & (cls < C)
+        if self.max_per_img is not None:
+            keep &= ops.rank_desc_images(joint, cls, det_off) < self.max_per_img
+        # (no compaction, which would be a host read: ops.pr_curves passes over the rows of class -1)
+        self._records.append((joint, gid, matched, torch.where(keep, cls, torch.full_like(cls, -1))))
+
+    def score_mat(self, precision_mode=None):
+        """create_score_mat's table of what update has seen (precision_mode None: the constructor's)"""
+        import pandas as pd
+        precision_mode = self.precision_mode if precision_mode is None else precision_mode
+        class_num = self.class_num
+        if self._counts is None:
+            c = np.zeros((class_num, 4))
+        else:
+            c = self._counts.cpu().numpy().astype(np.float64)   # dets, gts, tpp, tp
+        dets, gts, tpp, tp = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
+        denom_p = dets - (tpp - tp) if precision_mode == 1 else dets
+        num_p = tpp if precision_mode == 0 else tp
+        with np.errstate(divide="ignore", invalid="ignore"):
+            precision = np.true_divide(num_p, denom_p)
+            recall = np.true_divide(tp, gts)
+            f1 = (2 * precision * recall) / (precision + recall)
+        table = pd.DataFrame({"precision": precision, "recall": recall, "F1-score": f1,
+                              "gts": gts.astype("int"), "dets": dets.astype("int")})
+        table.index = self.class_names
+        return table
+
+    def _curves(self):
+        """(precisions, recalls): one float64 array per class, from one ops.pr_curves call"""
+        class_num = self.class_num
+        n_c = np.zeros(class_num + 1, dtype=np.int64)
+        gts_h = np.zeros(class_num, dtype=np.int64)
+        if self._gts is not None:
+            gts_h = self._gts.cpu().numpy()
+        if self._records:
+            joint, gid, matched, cls = (torch.cat(col) for col in zip(*self._records))
+            cls_off, prec, rec = ops.pr_curves(joint, gid, matched, cls, self._gts, self.precision_mode,
+                                               gts_total=self._gt_rows)
+            off = cls_off.cpu().numpy().astype(np.int64)
+            prec, rec = prec.cpu().numpy(), rec.cpu().numpy()
+            n_c = np.diff(off)
+        precisions, recalls = [], []
+        for c in range(class_num):
+            n, num_gts = int(n_c[c]), int(gts_h[c])
+            if n == 0:
+                precisions.append(np.array([0.0]))
+                recalls.append(np.array([0.0 if num_gts > 0 else np.nan]))
+            elif num_gts == 0:   # every detection is a false positive; recall undefined
+                precisions.append(np.zeros(n + 1))
+                recalls.append(np.full(n + 1, np.nan))
+            else:
+                first = int(off[c]) + c
+                precisions.append(prec[first:first + n + 1].copy())
+                recalls.append(rec[first:first + n + 1].copy())
+        return precisions, recalls
+
+    def prfunc(self):
+        """the PRfunc of what update has seen: __call__, plot_pr_curve and get_map as ever"""
+        f = PRfunc.__new__(PRfunc)
+        f.class_num, f.class_names = self.class_num, self.class_names
+        f.precisions, f.recalls = self._curves()
+        return f
+
+
+def _feed(ev, y_trues, y_preds, records):
+    """the arrays of a data set through ev in chunks of EVAL_CHUNK images"""
+    arrays = [a if torch.is_tensor(a) or isinstance(a, np.ndarray) else np.asarray(a) for a in (y_trues,) + tuple(y_preds)]
+    for i in range(0, len(arrays[0]), EVAL_CHUNK):
+        ev._update(arrays[0][i:i + EVAL_CHUNK], [a[i:i + EVAL_CHUNK] for a in arrays[1:]], records)
+    return ev
 
 
 def create_score_mat(y_trues, *y_preds, class_names=[], conf_threshold=0.5, nms_mode=0, nms_threshold=0.5,
                      nms_sigma=0.5, iou_threshold=0.5, precision_mode=2, version=3):
     """Score table (pandas.DataFrame: precision, recall, F1-score, gts, dets per class)."""
-    import pandas as pd
     if not torch.cuda.is_available():
         raise YoloHipError("tf2_yolo_amd.measurement needs a HIP device: there is no CPU fallback")
-    class_num = len(class_names)
-    counts = torch.zeros((max(class_num, 1), 4), device="cuda", dtype=torch.int64)
-    for y_true, y_pred in _images(y_trues, y_preds):
-        gt, det = _per_image_rows(y_true, y_pred, class_num, conf_threshold, nms_mode, nms_threshold, nms_sigma, version)
-        if class_num:
-            ops.match_detections(gt, det, class_num, iou_threshold, counts)
-    c = counts.cpu().numpy()[:class_num].astype(np.float64)   # dets, gts, tpp, tp
-    dets, gts, tpp, tp = c[:, 0], c[:, 1], c[:, 2], c[:, 3]
-    denom_p = dets - (tpp - tp) if precision_mode == 1 else dets
-    num_p = tpp if precision_mode == 0 else tp
-    with np.errstate(divide="ignore", invalid="ignore"):
-        precision = np.true_divide(num_p, denom_p)
-        recall = np.true_divide(tp, gts)
-        f1 = (2 * precision * recall) / (precision + recall)
-    table = pd.DataFrame({"precision": precision, "recall": recall, "F1-score": f1,
-                          "gts": gts.astype("int"), "dets": dets.astype("int")})
-    table.index = class_names
-    return table
+    ev = Evaluator(class_names, version=version, conf_threshold=conf_threshold, nms_mode=nms_mode, nms_threshold=nms_threshold,
+                   nms_sigma=nms_sigma, iou_threshold=iou_threshold, precision_mode=precision_mode, max_per_img=None)
+    return _feed(ev, y_trues, y_preds, False).score_mat()
 
 
 class PRfunc(object):
@@ -77,54 +182,12 @@ class PRfunc(object):
                  nms_sigma=0.5, iou_threshold=0.5, precision_mode=2, max_per_img=100, version=3):
         if not torch.cuda.is_available():
             raise YoloHipError("tf2_yolo_amd.measurement needs a HIP device: there is no CPU fallback")
-        class_num = len(class_names)
-        self.class_num = class_num
+        ev = Evaluator(class_names, version=version, conf_threshold=conf_threshold, nms_mode=nms_mode,
+                       nms_threshold=nms_threshold, nms_sigma=nms_sigma, iou_threshold=iou_threshold,
+                       precision_mode=precision_mode, max_per_img=max_per_img)
+        self.class_num = ev.class_num
         self.class_names = class_names
-        gts = torch.zeros(max(class_num, 1), device="cuda", dtype=torch.int64)   # running ground-truth count
-        scratch = torch.zeros((max(class_num, 1), 4), device="cuda", dtype=torch.int64)
-        joint_l, gid_l, matched_l, cls_l = [], [], [], []
-        for y_true, y_pred in _images(y_trues, y_preds):
-            gt, det = _per_image_rows(y_true, y_pred, class_num, conf_threshold, nms_mode, nms_threshold,
-                                      nms_sigma, version)
-            if not class_num:
-                continue
-            scratch.zero_()
-            best_gt, matched, _ = ops.match_detections(gt, det, class_num, iou_threshold, scratch)
-            if det.shape[0]:
-                cls = det[:, 5].to(torch.int64)
-                ok = (cls >= 0) & (cls < class_num)
-                clsc = cls.clamp(0, class_num - 1)
-                joint = (det[:, 4] * det[:, 6]).contiguous()
-                # ids are global per class: index inside the image's class subset + ground truths seen so far
-                gid = torch.where(scratch[clsc, 1] > 0, best_gt.to(torch.int64) + gts[clsc], torch.zeros_like(cls))
-                keep = ok
-                if max_per_img is not None:
-                    rank = ops.rank_desc(joint, cls.to(torch.int32))
-                    keep = keep & (rank < max_per_img)
-                joint_l.append(joint[keep]); gid_l.append(gid[keep].to(torch.int32))
-                matched_l.append(matched[keep]); cls_l.append(cls[keep])
-            gts += scratch[:, 1]
-        gts_h = gts.cpu().numpy()
-        if joint_l:
-            joint_a, gid_a = torch.cat(joint_l), torch.cat(gid_l)
-            matched_a, cls_a = torch.cat(matched_l), torch.cat(cls_l)
-        self.precisions, self.recalls = [], []
-        for c in range(class_num):
-            sel = (cls_a == c) if joint_l else None
-            n = int(sel.sum().item()) if sel is not None else 0
-            num_gts = int(gts_h[c])
-            if n == 0:
-                self.precisions.append(np.array([0.0]))
-                self.recalls.append(np.array([0.0 if num_gts > 0 else np.nan]))
-                continue
-            if num_gts == 0:   # every detection is a false positive; recall undefined
-                self.precisions.append(np.zeros(n + 1))
-                self.recalls.append(np.full(n + 1, np.nan))
-                continue
-            p, r = ops.pr_curve(joint_a[sel].contiguous(), gid_a[sel].contiguous(), matched_a[sel].contiguous(),
-                                num_gts, precision_mode)
-            self.precisions.append(p.cpu().numpy())
-            self.recalls.append(r.cpu().numpy())
+        self.precisions, self.recalls = _feed(ev, y_trues, y_preds, True)._curves()
 
     def __call__(self, recall, class_idx=0):
         if class_idx >= self.class_num:

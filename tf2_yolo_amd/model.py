@@ -369,6 +369,47 @@ class Model:
             res += per_image
         return res
 
+    def evaluate_detections(self, x, y, class_names, batch_size=32, precision="fp32", rescale=None, conf_threshold=0.05,
+                            nms_mode=1, nms_threshold=0.5, nms_sigma=0.5, iou_threshold=0.5, precision_mode=2,
+                            max_per_img=100):
+        """Images and labels in, a measurement.Evaluator out: predict's forward, then every chunk's head buffers go to
+        Evaluator.update in place (decode, NMS, matching and the per-image cap on the device) -- no prediction reaches the
+        host. score_mat() / prfunc() of the result equal create_score_mat / PRfunc on predict(x)'s arrays with the same
+        keywords. x: what predict takes (rescale: uint8 images at the network's size); a Sequence of (img, label) batches
+        brings its own labels, y=None. y: the label tensor create_score_mat takes, [N, gh, gw, info]; a list of levels, as
+        given to fit, stands for its last and finest one."""
+        from .measurement import Evaluator
+        precision_enum(precision)
+        if self.version not in (1, 2, 3, 4):
+            raise ValueError("evaluate_detections needs a detector: this model is a backbone classifier (version 0)")
+        class_num = next(u.C for u in self.net.units if u.kind == "head")
+        if len(class_names) != class_num:
+            raise ValueError(f"the model's heads have {class_num} classes, class_names has {len(class_names)}")
+        ev = Evaluator(class_names, version=self.version, conf_threshold=conf_threshold, nms_mode=nms_mode,
+                       nms_threshold=nms_threshold, nms_sigma=nms_sigma, iou_threshold=iou_threshold,
+                       precision_mode=precision_mode, max_per_img=max_per_img)
+        finest = lambda lab: lab[-1] if isinstance(lab, (list, tuple)) else lab
+        if y is None:
+            if not (hasattr(x, "__getitem__") and hasattr(x, "__len__")) or isinstance(x, (np.ndarray, torch.Tensor)):
+                raise ValueError("evaluate_detections: y=None needs a Sequence of (img, label) batches")
+            if rescale is not None:
+                raise TypeError("evaluate_detections with rescale= takes a uint8 array [N, h, w, 3] and y, not a Sequence")
+            chunks = ((_to_input(x[i][0]), finest(x[i][1])) for i in range(len(x)))
+        else:
+            y = finest(y)
+            if len(y) != len(x):
+                raise ValueError(f"x and y hold different numbers of images: {len(x)} and {len(y)}")
+            labels = (y[i:i + batch_size] for i in range(0, len(x), batch_size))
+            if rescale is not None:
+                images = (c for c, _g in self._prepared_chunks(x, batch_size, rescale, None, 128, "evaluate_detections"))
+            else:
+                images = (_to_input(x[i:i + batch_size]) for i in range(0, len(x), batch_size))
+            chunks = zip(images, labels)
+        for c, lab in chunks:
+            # (update reads the head buffers for the last time before its own last host read: the next infer may overwrite them)
+            ev.update(lab, *self.net.infer(c, precision=precision))
+        return ev
+
     # ---- training ----
     def compile(self, optimizer="adam", loss=None, metrics=None, **_):
         if isinstance(optimizer, str):

@@ -1483,6 +1483,78 @@ def pr_curve(joint, gt_id, matched, num_gts, precision_mode):
     return prec, rec
 
 
+# ---- the same for a whole data set (csrc/measure_batch.hip): no launch and no host read per image or class ----
+def _chk_off(off, what):
+    if not (off.is_cuda and off.dtype == torch.int32 and off.dim() == 1 and off.numel() >= 2 and off.is_contiguous()):
+        raise YoloHipError(f"{what}: offsets must be a contiguous int32 CUDA tensor [B + 1]")
+    return int(off.numel()) - 1
+
+
+def match_batch(gt_rows, gt_off, det_rows, det_off, class_num, iou_threshold, gts_seen, class_counts):
+    """gt_rows [ngt,7] / det_rows [ndet,7]: float64 CUDA tensors of B images, image-major; gt_off / det_off: int32 CUDA tensors
+    [B + 1] (decode_batch, nms_batch_select). gts_seen int64 [class_num] (the ground truths per class before this call; advanced),
+    class_counts int64 [class_num,4] (accumulated). Returns (best_gt int32, matched uint8, best_iou float64, gid int32), [ndet]
+    each: match_detections of every image, and the ground truth's id inside its class over the data set. No host read."""
+    dev = class_counts.device
+    ngt, ndet = int(gt_rows.shape[0]), int(det_rows.shape[0])
+    B = _chk_off(gt_off, "match_batch")
+    if _chk_off(det_off, "match_batch") != B:
+        raise YoloHipError("match_batch: gt_off and det_off hold different batch sizes")
+    if ((ngt and gt_rows.dtype != torch.float64) or (ndet and det_rows.dtype != torch.float64)
+            or class_counts.dtype != torch.int64 or class_counts.numel() != class_num * 4
+            or gts_seen.dtype != torch.int64 or gts_seen.numel() != class_num):
+        raise YoloHipError("match_batch: rows must be float64 [n,7], class_counts int64 [class_num,4], gts_seen int64 [class_num]")
+    lib = _lib.load()
+    best_gt = torch.empty(ndet, device=dev, dtype=torch.int32)
+    matched = torch.empty(ndet, device=dev, dtype=torch.uint8)
+    best_iou = torch.empty(ndet, device=dev, dtype=torch.float64)
+    gid = torch.empty(ndet, device=dev, dtype=torch.int32)
+    nbytes = int(lib.yolo_match_batch_workspace_bytes(ngt, B, class_num))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    check(lib.yolo_match_batch(_p(gt_rows.contiguous()) if ngt else None, ngt, _p(gt_off),
+                               _p(det_rows.contiguous()) if ndet else None, ndet, _p(det_off), B, class_num,
+                               float(iou_threshold), _p(gts_seen), _p(best_gt), _p(matched), _p(best_iou), _p(gid),
+                               _p(class_counts), _p(ws), nbytes, _stream()), "yolo_match_batch")
+    return best_gt, matched, best_iou, gid
+
+
+def rank_desc_images(key, cls, img_off):
+    """rank_desc with segment = (image, cls): key float64 [n] of B images, image-major; cls int32 [n] or None; img_off int32
+    CUDA tensor [B + 1]. A row meets the rows of its own image only."""
+    n = int(key.numel())
+    B = _chk_off(img_off, "rank_desc_images")
+    rank = torch.empty(n, device=key.device, dtype=torch.int32)
+    if n:
+        if key.dtype != torch.float64 or (cls is not None and (cls.dtype != torch.int32 or cls.numel() != n)):
+            raise YoloHipError("rank_desc_images: key must be float64 [n], cls int32 [n]")
+        check(_lib.load().yolo_rank_desc_images(_p(key.contiguous()), _p(cls.contiguous()) if cls is not None else None, n,
+                                                _p(img_off), B, _p(rank), _stream()), "yolo_rank_desc_images")
+    return rank
+
+
+def pr_curves(joint, gid, matched, cls, gts, precision_mode, gts_total=None):
+    """pr_curve of every class in one call: joint float64, gid int32, matched uint8, cls int32, [n] each (rows with a class
+    outside [0, C) are passed over); gts int64 CUDA tensor [C]. gts_total: an upper bound of gts.sum() known on the host (None:
+    it is read from the device). Returns (cls_off int32 [C + 1], precision, recall float64 [n + C]) on the device: class c's
+    n_c + 1 points start at cls_off[c] + c; the slots of a class with n_c = 0 or gts[c] = 0 are not written."""
+    n, C, dev = int(joint.numel()), int(gts.numel()), gts.device
+    if (joint.dtype != torch.float64 or gid.dtype != torch.int32 or matched.dtype != torch.uint8 or cls.dtype != torch.int32
+            or gts.dtype != torch.int64 or not (gid.numel() == matched.numel() == cls.numel() == n)):
+        raise YoloHipError("pr_curves: joint float64, gid int32, matched uint8, cls int32 of one length and gts int64 expected")
+    if gts_total is None:
+        gts_total = int(gts.clamp(min=0).sum().item())
+    lib = _lib.load()
+    nbytes = int(lib.yolo_pr_curves_workspace_bytes(n, C, int(gts_total)))
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    cls_off = torch.empty(C + 1, device=dev, dtype=torch.int32)
+    prec = torch.empty(n + C, device=dev, dtype=torch.float64)
+    rec = torch.empty(n + C, device=dev, dtype=torch.float64)
+    check(lib.yolo_pr_curves(_p(joint.contiguous()), _p(gid.contiguous()), _p(matched.contiguous()), _p(cls.contiguous()), n,
+                             _p(gts.contiguous()), C, int(gts_total), int(precision_mode), _p(ws), nbytes, _p(cls_off),
+                             _p(prec), _p(rec), _stream()), "yolo_pr_curves")
+    return cls_off, prec, rec
+
+
 # ---- stand-alone cal_iou (csrc/iou.hip) -------------------------------------------------------------------
 def cal_iou(xywh_true, xywh_pred, mode=1, grid_wh=(1.0, 1.0)):
     """Broadcasting IoU (mode 1) / DIoU (2) / (IoU, CIoU) (3) of boxes [..., >=4] (x, y, w, h first); both CUDA tensors of
