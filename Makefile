@@ -4,7 +4,7 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := tf2_yolo_amd/csrc
 SRCS  := $(CSRC)/runtime.hip $(CSRC)/probe.hip $(CSRC)/conv.hip $(CSRC)/conv_split.hip $(CSRC)/conv_wgrad_split.hip $(CSRC)/conv_planes.hip $(CSRC)/conv_win.hip $(CSRC)/conv_small.hip $(CSRC)/conv_wgrad_planes.hip $(CSRC)/conv_wgrad_win.hip $(CSRC)/stem.hip $(CSRC)/bn_act.hip $(CSRC)/elementwise.hip \
-         $(CSRC)/labels.hip $(CSRC)/loss.hip $(CSRC)/decode_nms.hip $(CSRC)/iou.hip $(CSRC)/measure.hip $(CSRC)/measure_batch.hip $(CSRC)/optim.hip $(CSRC)/classify.hip $(CSRC)/image.hip
+         $(CSRC)/labels.hip $(CSRC)/loss.hip $(CSRC)/decode_nms.hip $(CSRC)/iou.hip $(CSRC)/measure.hip $(CSRC)/optim.hip $(CSRC)/classify.hip $(CSRC)/image.hip
 OBJS  := $(SRCS:.hip=.o)
 LIB   := tf2_yolo_amd/libyolo_hip.so
 HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -munsafe-fp-atomics -Wall -Wno-unused-function

@@ -772,7 +772,8 @@ int yolo_cal_iou(const void* xywh_true, const void* xywh_pred, void* out, void* 
  * class, np.argmax = first maximum) of the ground truth with the highest IoU, matched = that IoU >=
  * iou_threshold, best_iou (0 / 0 / 0 when the class has no ground truth: measurement.py:275-277).
  * class_counts[c*4 + {0,1,2,3}] += #detections, #ground truths, #matched detections, #distinct matched
- * ground truths of class c (accumulates over images; zero it first). gt_flags: scratch of ngt bytes. */
+ * ground truths of class c (accumulates over images; zero it first). gt_flags: scratch of ngt bytes (it need not
+ * be initialised). */
 int yolo_match_detections(const double* gt_rows, int ngt, const double* det_rows, int ndet, int class_num,
                           double iou_threshold, int* best_gt, unsigned char* matched, double* best_iou,
                           unsigned char* gt_flags, long long* class_counts, void* stream);
@@ -796,8 +797,9 @@ int yolo_pr_curve(const double* joint, const int* gt_id, const unsigned char* ma
                   int precision_mode, void* workspace, size_t workspace_bytes, double* precision,
                   double* recall, void* stream);
 
-/* The three calls above for a whole data set (csrc/measure_batch.hip): no launch and no device read per image or per
- * class. Every value equals what the per-image / per-class call gives, bit for bit.
+/* The three calls above for a whole data set: no launch and no device read per image or per class. Every value equals
+ * what the per-image / per-class call gives, bit for bit: csrc/measure.hip has one set of kernels, and the calls above
+ * run them for one image or one class.
  *
  * yolo_match_batch: rows of B images, image-major, with device offsets gt_off / det_off (int [B + 1], [B] = the row
  * count) -- what yolo_decode_batch_write and yolo_nms_batch_select store. Per detection best_gt / matched / best_iou as

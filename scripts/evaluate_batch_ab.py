@@ -9,6 +9,12 @@ every such cell is a ground truth with that box and its best class. Rows, each o
   predict_then_prfunc           Model.predict (every level to the host) + PRfunc + get_map()
   evaluate_detections           Model.evaluate_detections + prfunc() + get_map() + score_mat(): only where the tree has it
 
+and the one-image / one-class entry points, which no row above calls, each one call on seeded rows:
+
+  one_match_detections          ops.match_detections, 300 ground truths and 700 detections of 3 classes
+  one_rank_desc                 ops.rank_desc, 3100 rows in seven segments
+  one_pr_curve                  ops.pr_curve, 3100 rows and 300 ground truths, precision mode 2
+
 "Before" is a second checkout (the parent commit, built) given with --before; "after" is the tree this script lies in. Every
 measurement is a fresh process of one tree: one untimed call per row, then `calls` timed ones, host clock around synchronised
 calls. The processes of the two trees alternate, `rounds` each, in one session on one box; the file keeps every sample, the
@@ -118,10 +124,33 @@ def child(calls, images):
         assert digest(np, f) == seen["curves"]
         assert hashlib.sha256(t.to_numpy().astype(np.float64).tobytes()).hexdigest() == seen["table"]
 
+    from tf2_yolo_amd import ops
+    rng = np.random.default_rng(4321)
+    gt = np.concatenate((rng.random((300, 2)) * 0.8 + 0.1, rng.random((300, 2)) * 0.25 + 0.05, np.ones((300, 1)),
+                         rng.integers(0, 3, (300, 1)), np.ones((300, 1))), axis=1)
+    det = gt[rng.integers(0, 300, 700)]                   # noisy copies: several detections per ground truth
+    det[:, :4] *= 1 + rng.normal(0, 0.05, (700, 4))
+    det[:, 4], det[:, 6] = rng.random(700), rng.random(700)
+    one = [rng.random(3100), rng.integers(0, 7, 3100).astype(np.int32), rng.integers(0, 300, 3100).astype(np.int32),
+           (rng.random(3100) < 0.5).astype(np.uint8)]
+    gt, det, key, seg, gid, hit = (torch.from_numpy(a).cuda() for a in [gt, det] + one)
+    last = {}
+
+    def one_match_detections():
+        counts = torch.zeros((3, 4), device="cuda", dtype=torch.int64)
+        last["one_match"] = ops.match_detections(gt, det, 3, 0.5, counts) + (counts,)
+
+    def one_rank_desc():
+        last["one_rank"] = (ops.rank_desc(key, seg),)
+
+    def one_pr_curve():
+        last["one_curve"] = ops.pr_curve(key, gid, hit, 300, 2)
+
     rows = [("prfunc_host_arrays", prfunc_host), ("score_mat_host_arrays", score_mat_host),
             ("predict_then_prfunc", predict_then_prfunc)]
     if hasattr(m, "evaluate_detections"):
         rows.append(("evaluate_detections", evaluate_detections))
+    rows += [("one_match_detections", one_match_detections), ("one_rank_desc", one_rank_desc), ("one_pr_curve", one_pr_curve)]
     out = {}
     for name, fn in rows:
         fn()                                  # untimed: code objects, the caching allocator, the host buffers
@@ -133,6 +162,8 @@ def child(calls, images):
             torch.cuda.synchronize()
             ms.append((time.perf_counter() - t0) * 1e3)
         out[name] = ms
+    for name, tensors in last.items():        # what the one-image / one-class calls gave: equal in both trees, like the curves
+        seen[name] = hashlib.sha256(b"".join(t.cpu().numpy().tobytes() for t in tensors)).hexdigest()
     print(json.dumps({"ms": out, "seen": seen, "conf_threshold": thr, "device": torch.cuda.get_device_name(0)}), flush=True)
 
 
@@ -172,7 +203,7 @@ def main():
     def compare(name, b, a_):
         lo, hi = (a_, b) if a_["median"] <= b["median"] else (b, a_)
         return {"row": name, "before_ms": b["median"], "after_ms": a_["median"], "speedup": b["median"] / a_["median"],
-                "within_spread": lo["max"] >= hi["min"]}
+                "within_spread": lo["max"] >= hi["min"], "after_median_within_or_below_before_range": a_["median"] <= b["max"]}
     cmp_ = [compare(k, res["before"][k], res["after"][k]) for k in res["before"]]
     cmp_.append(compare("predict_then_prfunc (before) -> evaluate_detections (after)", res["before"]["predict_then_prfunc"],
                         res["after"]["evaluate_detections"]))

@@ -4,13 +4,14 @@ from the source; tests/test_gpu_measure_kernels.py and tests/test_gpu_measuremen
 
 The kernels work in tiles:
 
-  rank tile    rank_desc_kernel walks the keys in tiles of 256; one workgroup covers 256 rows
-  launch tile  match_kernel (and every other grid of measure.hip) is a grid of 256-thread workgroups
-  count tile   match_counts_kernel is ONE workgroup striding by 256 over detections and ground truths
-  scan chunk   pr_scan_kernel walks the sorted flags in chunks of 1024 and carries a running (tpp, tp) pair
+  rank tile    rank_desc_images_kernel walks the keys in tiles of 256; one workgroup covers 256 rows
+  launch tile  mb_match_kernel over the detections, mb_distinct_kernel over the ground truths (and every other grid over
+               rows of measure.hip) is a grid of 256-thread workgroups
+  scan chunk   prc_scan_kernel walks the sorted flags in chunks of 1024 and carries a running (tpp, tp) pair
 
 Size rule: the boundary cases sit at tile - 1, tile, tile + 1; a "past one tile" case has more than 256 detections and more
-than 256 ground truths in one image and more than 2 x 1024 detections of one class (a first, a middle and a last chunk).
+than 256 ground truths in one image (a second workgroup of both grids) and more than 2 x 1024 detections of one class (a
+first, a middle and a last chunk).
 
 The order (ref_rank_desc, ref_order): keys descend; the order key of NaN is +inf (np.argsort puts NaN last, so the
 reference's argsort()[::-1] visits it first); equal order keys -- -0.0 and 0.0, two NaNs, NaN and +inf -- put the HIGHER
@@ -29,10 +30,9 @@ import gen_inputs                                    # noqa: E402
 from oracle import measurement as OM                  # noqa: E402
 from oracle import tools as OT                        # noqa: E402
 
-RANK_TILE = 256          # rank_desc_kernel: rows per LDS tile and per workgroup
-LAUNCH_BLOCK = 256       # threads per workgroup of every grid launch
-COUNT_STRIDE = 256       # match_counts_kernel: one workgroup, stride of its loops
-SCAN_CHUNK = 1024        # pr_scan_kernel: flags per chunk
+RANK_TILE = 256          # rank_desc_images_kernel: rows per LDS tile and per workgroup
+LAUNCH_BLOCK = 256       # threads per workgroup of every grid over rows (detections, ground truths, classes)
+SCAN_CHUNK = 1024        # prc_scan_kernel: flags per chunk
 MARGIN = 1e-9            # no reference IoU of a match case lies this close to the case's threshold
 
 

@@ -1,4 +1,4 @@
-"""Data-set evaluation on the device (measurement.Evaluator, Model.evaluate_detections, csrc/measure_batch.hip) without a
+"""Data-set evaluation on the device (measurement.Evaluator, Model.evaluate_detections, csrc/measure.hip) without a
 device: the C entry points are declared, exported and bound, their size queries answer on the host, bad arguments and a
 short workspace are refused before any launch, and the Python argument errors come before anything touches the GPU."""
 import ctypes
@@ -43,14 +43,14 @@ def test_new_entry_points_are_declared_exported_and_bound():
 
 
 def test_shared_device_helpers_are_stated_once():
-    """iou_xywh and desc_order_key live in headers that both kernel files include"""
-    src = {n: open(os.path.join(ROOT, "tf2_yolo_amd", "csrc", n)).read()
-           for n in ("measure.hip", "measure_batch.hip", "measure_common.hpp", "common.hpp")}
-    for body, home in (("double iou_xywh(", "measure_common.hpp"), ("double desc_order_key(", "common.hpp")):
+    """one evaluation source: iou_xywh is defined once under csrc/, in measure.hip, and desc_order_key once, in common.hpp"""
+    csrc = os.path.join(ROOT, "tf2_yolo_amd", "csrc")
+    src = {n: open(os.path.join(csrc, n)).read() for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".hpp"))}
+    for body, home in (("double iou_xywh(", "measure.hip"), ("double desc_order_key(", "common.hpp")):
         assert [n for n, s in src.items() if body in s] == [home]
-    for n in ("measure.hip", "measure_batch.hip"):
-        assert '#include "measure_common.hpp"' in src[n] and "iou_xywh(" in src[n] and "desc_order_key(" in src[n]
-    assert "measure_batch.hip" in open(os.path.join(ROOT, "Makefile")).read()
+    assert '#include "common.hpp"' in src["measure.hip"] and "desc_order_key(" in src["measure.hip"]
+    make = open(os.path.join(ROOT, "Makefile")).read()
+    assert "$(CSRC)/measure.hip" in make and "measure_batch" not in make
 
 
 def test_workspace_queries():

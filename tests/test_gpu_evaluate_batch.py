@@ -1,6 +1,6 @@
-"""Data-set evaluation on the device: the kernels of tf2_yolo_amd/csrc/measure_batch.hip through ops (match_batch,
+"""Data-set evaluation on the device: the kernels of tf2_yolo_amd/csrc/measure.hip through ops (match_batch,
 rank_desc_images, pr_curves) against the NumPy references of tests/measure_cases.py and against the per-image / per-class
-kernels they batch; measurement.Evaluator against the oracle and the reference's own outputs (golden), fed in chunks of 1,
+front ends of the same kernels; measurement.Evaluator against the oracle and the reference's own outputs (golden), fed in chunks of 1,
 7 and all images; Model.evaluate_detections against PRfunc / create_score_mat on predict's arrays. Every comparison is exact
 (NaNs positionally), except best_iou against NumPy, where the existing kernel test allows the compiler's fused multiply-adds.
 

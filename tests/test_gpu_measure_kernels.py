@@ -1,7 +1,7 @@
-"""The evaluation kernels (tf2_yolo_amd/csrc/measure.hip) through ops, one by one, against the float64 NumPy references of
-tests/measure_cases.py: at the tile edges (255 / 256 / 257 rows, 1023 / 1024 / 1025 sorted flags), past them (several rank
-tiles, a second workgroup of every grid, the strided loops of the count kernel, the chunk carry of the scan), with score
-ties, NaN scores and class ids outside the range. tests/test_measure_cases_cpu.py guards the table without a GPU."""
+"""The evaluation kernels (tf2_yolo_amd/csrc/measure.hip) through the one-image / one-class front ends of ops, one by one,
+against the float64 NumPy references of tests/measure_cases.py: at the tile edges (255 / 256 / 257 rows, 1023 / 1024 / 1025
+sorted flags), past them (several rank tiles, a second workgroup of every grid over detections and ground truths, the
+chunk carry of the scan), with score ties, NaN scores and class ids outside the range. tests/test_measure_cases_cpu.py guards the table without a GPU."""
 import numpy as np
 import pytest
 import torch
@@ -59,6 +59,65 @@ def test_match_detections(case):
         assert np.array_equal(acc.cpu().numpy(), call * counts), call
 
 
+@pytest.mark.parametrize("name", ["gt300-det700", "gt1-det1"])
+def test_match_detections_zeroes_the_callers_flags(name):
+    """gt_flags comes uninitialised: the raw call with the flags full of 0xFF, twice into the same class_counts, counts
+    what the reference counts, and leaves one flag per distinct matched ground truth of a class in range"""
+    from tf2_yolo_amd import _lib, ops
+    case = MC.MATCH_BY_NAME[name]
+    gt, det = (_dev(a) for a in MC.match_case(name))
+    counts = MC.match_reference(name)[3]
+    lib = _lib.load()
+    acc = torch.zeros((MC.MATCH_CLASSES, 4), device="cuda", dtype=torch.int64)
+    best_gt = torch.empty(case.ndet, device="cuda", dtype=torch.int32)
+    matched = torch.empty(case.ndet, device="cuda", dtype=torch.uint8)
+    best_iou = torch.empty(case.ndet, device="cuda", dtype=torch.float64)
+    for call in (1, 2):
+        flags = torch.full((case.ngt,), 0xFF, device="cuda", dtype=torch.uint8)
+        assert lib.yolo_match_detections(ops._p(gt), case.ngt, ops._p(det), case.ndet, MC.MATCH_CLASSES, float(case.thr),
+                                         ops._p(best_gt), ops._p(matched), ops._p(best_iou), ops._p(flags), ops._p(acc),
+                                         ops._stream()) == 0
+        assert np.array_equal(acc.cpu().numpy(), call * counts), call
+        assert int(flags.max()) <= 1 and int(flags.sum()) == counts[:, 3].sum(), call
+
+
+@pytest.mark.parametrize("name", ["gt300-det0", "gt0-det300"])
+def test_match_detections_with_one_side_empty(name):
+    """no detections: only the ground-truth column of the counts advances; no ground truths: only the detection column, and
+    nothing is matched (both cases are rows of MC.MATCH_CASES, so test_match_detections holds them to the reference too)"""
+    from tf2_yolo_amd import ops
+    case = MC.MATCH_BY_NAME[name]
+    gt, det = MC.match_case(name)
+    acc = torch.zeros((MC.MATCH_CLASSES, 4), device="cuda", dtype=torch.int64)
+    for call in (1, 2):
+        _, g_matched, _ = ops.match_detections(_dev(gt), _dev(det), MC.MATCH_CLASSES, case.thr, acc)
+        got = acc.cpu().numpy()
+        side, rows = (1, gt) if case.ndet == 0 else (0, det)
+        assert np.array_equal(got[:, side], call * np.bincount(rows[:, 5].astype(int), minlength=MC.MATCH_CLASSES)), call
+        assert got[:, side].sum() == call * len(rows) and not np.delete(got, side, axis=1).any(), call
+        assert g_matched.shape == (case.ndet,) and not g_matched.any()
+
+
+def test_rank_desc_hostile_segment_ids():
+    """segment ids are any ints, compared for equality only: negative ones, INT_MIN and INT_MAX, interleaved, one row past a
+    tile, with a tie run across the tile edge and one NaN -- no id is a padding marker of the kernel"""
+    from tf2_yolo_amd import ops
+    n = MC.RANK_TILE + 1
+    rng = np.random.default_rng(257)
+    ids = np.array([-3, -2, -1, 0, 2**31 - 1, -2**31], dtype=np.int64)
+    seg = ids[rng.permutation(np.arange(n) % len(ids))].astype(np.int32)
+    key = rng.random(n)
+    key[MC.RANK_TILE - 16:] = 0.5                              # rows 240 .. 256: a tie run of every segment across the edge
+    key[7] = np.nan
+    assert set(seg) == set(ids) and (np.diff(seg) != 0).sum() > n // 2
+    assert (seg[MC.RANK_TILE - 16:MC.RANK_TILE] == seg[MC.RANK_TILE]).any()      # the last row ties with rows of the first tile
+    got = ops.rank_desc(_dev(key), _dev(seg)).cpu().numpy()
+    for s in ids:
+        rows = got[seg == s]
+        assert np.array_equal(np.sort(rows), np.arange(len(rows))), s
+    assert np.array_equal(got, MC.ref_rank_desc(key, seg))
+
+
 # ---- ops.pr_curve ---------------------------------------------------------------------------------------------------
 def _pr(n, num_gts, kind, mode, poison=False):
     from tf2_yolo_amd import _lib, ops
@@ -105,6 +164,19 @@ def test_pr_curve_nan_scores(n, num_gts, mode):
     """NaN scores order as +inf. Without a total order the ranks are no permutation and slots of the sorted flags stay
     unwritten: the workspace's memory is filled with 0xFF beforehand so that such a slot shows"""
     _pr(n, num_gts, "nan", mode, poison=True)
+
+
+@pytest.mark.parametrize("n,num_gts", [(1, 1), (1025, 300)])
+def test_pr_curve_is_pr_curves_of_a_one_class_data_set(n, num_gts):
+    """the by-value class of yolo_pr_curve against the device tables of yolo_pr_curves: the same n + 1 points"""
+    from tf2_yolo_amd import ops
+    joint, gid, matched = (_dev(a) for a in MC.pr_case(n, num_gts, "mixed"))
+    p, r = ops.pr_curve(joint, gid, matched, num_gts, 1)
+    cls = torch.zeros(n, device="cuda", dtype=torch.int32)
+    gts = torch.tensor([num_gts], device="cuda", dtype=torch.int64)
+    cls_off, ps, rs = ops.pr_curves(joint, gid, matched, cls, gts, 1)
+    assert cls_off.tolist() == [0, n] and p.shape == (n + 1,)
+    assert torch.equal(ps, p) and torch.equal(rs, r)
 
 
 def test_pr_curve_rejections():

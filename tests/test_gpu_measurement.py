@@ -156,8 +156,8 @@ def test_many_images_against_oracle(precision_mode):
 
 @pytest.mark.parametrize("iou_threshold", MC.DENSE_THRESHOLDS)
 def test_dense_images_against_oracle(iou_threshold):
-    """two images with 400 ground truths and about 700 detections each: the second and third workgroup of match_kernel,
-    the strided loops of match_counts_kernel, three rank tiles, and a per-image cap of 100 that really cuts (more than 200
+    """two images with 400 ground truths and about 700 detections each: the second and third workgroup of mb_match_kernel,
+    the second workgroup of mb_distinct_kernel, three rank tiles, and a per-image cap of 100 that really cuts (more than 200
     detections per class and image)"""
     from utils.measurement import PRfunc, create_score_mat
     y_true, lv0, lv1 = MC.dense_inputs()

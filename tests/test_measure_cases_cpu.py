@@ -34,27 +34,31 @@ def _kernel(src, name):
 
 def test_tiles_in_the_source_are_the_tiles_of_the_table():
     src = _src()
-    rank = _kernel(src, "rank_desc_kernel")
+    rank = _kernel(src, "rank_desc_images_kernel")
     assert set(re.findall(r"base \+= (\d+)", rank)) == {str(MC.RANK_TILE)}
-    assert set(re.findall(r"__shared__ \w+ s_\w+\[(\d+)\]", rank)) == {str(MC.RANK_TILE)}
-    assert re.search(r"blockIdx\.x \* %d \+ threadIdx\.x" % MC.RANK_TILE, rank)
-    counts = _kernel(src, "match_counts_kernel")
-    strides = re.findall(r"\+= (\d+)\)", counts)
-    assert len(strides) == 3 and set(strides) == {str(MC.COUNT_STRIDE)}, strides
-    scan = _kernel(src, "pr_scan_kernel")
+    lds = dict(re.findall(r"__shared__ \w+ (s_\w+)\[(\d+)\]", rank))
+    assert lds == {"s_key": str(MC.RANK_TILE), "s_cls": str(MC.RANK_TILE), "s_range": "2"}, lds      # two tiles and one range
+    assert re.search(r"w0 = blockIdx\.x \* %d;" % MC.RANK_TILE, rank) and "i = w0 + threadIdx.x;" in rank
+    assert re.search(r"__launch_bounds__\(%d\) void rank_desc_images_kernel" % MC.RANK_TILE, src)
+    scan = _kernel(src, "prc_scan_kernel")
     assert set(re.findall(r"base \+= (\d+)", scan)) == {str(MC.SCAN_CHUNK)}
-    assert re.search(r"__launch_bounds__\(%d\) void pr_scan_kernel" % MC.SCAN_CHUNK, src)
+    assert re.search(r"__launch_bounds__\(%d\) void prc_scan_kernel" % MC.SCAN_CHUNK, src)
+    assert re.findall(r"__shared__ int s_w\[(\d+)\]", scan) == [str(MC.SCAN_CHUNK // 64)]            # one count per wave
+    # every launch of the file is written so that this pattern reads it: one that it cannot read is a failure, not a skip
     launches = re.findall(r"hipLaunchKernelGGL\((\w+), dim3\((.*?)\), dim3\((\d+)\), 0,", src)
+    assert len(launches) == src.count("hipLaunchKernelGGL") == 16, launches
     kernels = set(re.findall(r"__global__[^;{]*?void (\w+)\(", src))
-    assert len(kernels) == 7 and {name for name, _, _ in launches} == kernels and len(launches) == 8, launches
+    assert len(kernels) == 12 and {name for name, _, _ in launches} == kernels, (kernels, launches)
+    per_class = {"prc_scan_kernel": MC.SCAN_CHUNK,          # one workgroup per class: the chunk carry stays in registers
+                 "prc_partition_kernel": MC.SCAN_CHUNK}     # one workgroup per class: the same 16-wave prefix count
     for name, grid, block in launches:
-        if name == "pr_scan_kernel":
-            assert (grid, int(block)) == ("1", MC.SCAN_CHUNK)
-        elif name == "match_counts_kernel":
-            assert (grid, int(block)) == ("1", MC.COUNT_STRIDE)
+        if name in per_class:
+            assert grid in ("C", "class_num") and int(block) == per_class[name], (name, grid, block)
+        elif name == "prc_offsets_kernel":                  # one thread scans the class counts: C is small
+            assert (grid, int(block)) == ("1", 64)
         else:
-            assert int(block) == MC.LAUNCH_BLOCK and re.fullmatch(r"\(\w+ \+ %d\) / %d" % (int(block) - 1, int(block)), grid), \
-                (name, grid, block)
+            assert int(block) == MC.LAUNCH_BLOCK, (name, grid, block)
+            assert re.fullmatch(r"(?:\(unsigned\)\()?\(\w+ \+ %d\) / %d\)?" % (int(block) - 1, int(block)), grid), (name, grid)
 
 
 def test_kernel_cases_sit_on_the_tile_edges_and_past_them():
@@ -64,7 +68,7 @@ def test_kernel_cases_sit_on_the_tile_edges_and_past_them():
     b = MC.LAUNCH_BLOCK
     assert {0, 1, b - 1, b, b + 1} <= dets and {0, 1} <= gts
     big = MC.MATCH_BY_NAME["gt300-det700"]
-    assert big.ngt > MC.COUNT_STRIDE and big.ndet > 2 * max(MC.COUNT_STRIDE, b)
+    assert big.ngt > b and big.ndet > 2 * b       # a second workgroup over the ground truths, a third over the detections
     s = MC.SCAN_CHUNK
     assert {1, s - 1, s, s + 1} <= set(MC.PR_NS)
     assert sum(2 * s < n <= 3 * s for n in MC.PR_NS) >= 1 and max(MC.PR_NS) > 3 * s
@@ -234,11 +238,13 @@ def test_tied_fixture_has_ties_where_the_cut_and_the_curve_decide():
 
 
 def test_dense_fixture_lies_past_the_launch_and_count_tiles():
+    """more than one 256-thread workgroup over the detections (mb_match_kernel) and over the ground truths, which
+    mb_distinct_kernel counts, of ONE image"""
     y_true, lv0, lv1 = MC.dense_inputs()
     rows = MC.image_rows(y_true, (lv0, lv1), MC.DENSE_CLASSES, **MC.DENSE_KW)
     per_image = [len(d) for _, d in rows]
     print(f"MEASURE_SIZES dense: detections per image {per_image}, ground truths per image {[len(g) for g, _ in rows]}")
-    assert min(per_image) > 2 * MC.LAUNCH_BLOCK and all(len(g) == 400 > MC.COUNT_STRIDE for g, _ in rows)
+    assert min(per_image) > 2 * MC.LAUNCH_BLOCK and all(len(g) == 400 > MC.LAUNCH_BLOCK for g, _ in rows)
     for _, det in rows:       # the cap of 100 per image and class really cuts
         assert (np.bincount(det[:, 5].astype(int), minlength=3) > 2 * MC.DENSE_KW["max_per_img"]).all()
     for thr in MC.DENSE_THRESHOLDS:

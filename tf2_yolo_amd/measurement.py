@@ -2,7 +2,7 @@
 
 Same names, arguments, defaults and return types (pandas DataFrames; PRfunc.precisions / .recalls lists of
 float64 arrays). The pipeline is decode -> NMS -> IoU matching -> per-image cap, for a chunk of images at a time and
-all in HIP kernels (decode_nms.hip, measure_batch.hip); the precision / recall curves of all classes are one more call over
+all in HIP kernels (decode_nms.hip, measure.hip); the precision / recall curves of all classes are one more call over
 the detections of the whole data set. `Evaluator` is that pipeline as an accumulator (update per chunk, score_mat /
 prfunc at the end; Model.evaluate_detections feeds it the head buffers in place); create_score_mat and PRfunc cut their
 arrays into chunks of EVAL_CHUNK images and feed one. Nothing is launched or read back per image or per class.

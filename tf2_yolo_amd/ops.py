@@ -1437,7 +1437,7 @@ def nms_batch_select(rows, img_off, class_num, mode, nms_threshold, conf_thresho
     return out[:int(offs[B])], offs
 
 
-# ---- evaluation after decode / NMS (csrc/measure.hip) ---------------------------------------------------
+# ---- evaluation after decode / NMS (csrc/measure.hip): one image, one class -- the data-set kernels below for B = 1 ----
 def match_detections(gt_rows, det_rows, class_num, iou_threshold, class_counts):
     """gt_rows [ngt,7], det_rows [ndet,7] float64 CUDA tensors of ONE image; class_counts int64 CUDA tensor
     [class_num,4] (accumulated). Returns (best_gt int32 [ndet], matched uint8 [ndet], best_iou float64 [ndet])."""
@@ -1483,7 +1483,7 @@ def pr_curve(joint, gt_id, matched, num_gts, precision_mode):
     return prec, rec
 
 
-# ---- the same for a whole data set (csrc/measure_batch.hip): no launch and no host read per image or class ----
+# ---- the same for a whole data set (the same kernels of csrc/measure.hip): no launch and no host read per image or class ----
 def _chk_off(off, what):
     if not (off.is_cuda and off.dtype == torch.int32 and off.dim() == 1 and off.numel() >= 2 and off.is_contiguous()):
         raise YoloHipError(f"{what}: offsets must be a contiguous int32 CUDA tensor [B + 1]")
